@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: RCAN training tiles/s on MI355X (BASELINE.json metric, config 2/3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU, RCCL)
 
 Workload (BASELINE configs[1], weak-scaled for N>1 = configs[2]): rcan-10-20-64
@@ -12,13 +12,18 @@ baseline RMSE -> backward -> (RCCL loss + gradient all-reduce) -> Adam ->
 bf16 filter repack: exactly dual_trainer.py:310-323.
 Inputs are synthetic lnorm'ed N(0,1) tiles already resident in HBM.
 
-Prints ONE JSON line on rank 0 with the roofline of the dominant kernel
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0
+(metric, value, ms_per_step, per-step event times, loss); --dump-outputs DIR also
+writes what the last timed step computed (dump_outputs).  Everything else is behind
+--full: the same line then also holds the roofline of the dominant kernel
 (the fused conv1 dgrad + filter-gradient launch of the RCAB backward, re-issued
 by the bench's own engines at the in-step configuration and timed with HIP
 events on their streams after the timed region; conv2's fused launch and the
-isolated forward conv alongside; the step-level MFMA fraction) and the CPU baseline
-(the oracle, a PyTorch-CPU restatement of the reference step, timed on this
-host's cores on a bounded sample).
+isolated forward conv alongside; the step-level MFMA fraction), the idle-device host
+enqueue time, the one-rank DP overhead, the C4 EDSR and C5 inference lines and the CPU
+baseline (the oracle, a PyTorch-CPU restatement of the reference step, timed on this
+host's cores on a bounded sample).  The --no-* switches and --no-train select among
+the --full legs.
 """
 from __future__ import annotations
 
@@ -75,7 +80,14 @@ def parse():
                     help="A/B: the CA backward writes du for the conv2 backward to read (SRMI_FLAG_DU_PASS)")
     ap.add_argument("--no-rcab-infer", action="store_true",
                     help="A/B: inference RCABs as three launches (SRMI_FLAG_NO_RCAB_INFER)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: rooflines, idle host enqueue, DP overhead, C4 EDSR, C5 inference, CPU baseline")
+    args = ap.parse_args()
+    if args.no_train and not args.full:
+        ap.error("--no-train leaves only legs of --full: add --full")
+    return args
 
 
 def synthetic_hr(batch, nchan, size, seed):
@@ -518,6 +530,32 @@ def dp_overhead_probe(args, reps=2):
                       f"{args.steps} steps"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # all dumped arrays together
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, tr, out):
+    """What the last step of `tr` handed its caller, as float32 <name>.npy under
+    `path`: the step's return values (`loss`, `interp_loss`: the batch RMSE of the
+    network and of the bicubic baseline) and the network output of that step's batch
+    (`sr` [B, C, 192, 192], the trainer's output buffer).  Inputs and initial weights
+    are seeded, so two builds run with the same arguments write comparable files.
+    Above the byte budget `sr` is a fixed sample: elements of the flattened array at
+    sorted indices drawn without replacement from RandomState(DUMP_SAMPLE_SEED)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    sr = tr.sr.detach().float().cpu().numpy()
+    room = (DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values()) - 4096) // 4
+    if sr.size > room:
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(sr.size, room, replace=False))
+        sr = sr.reshape(-1)[idx]
+    arrays["sr"] = sr
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
@@ -582,6 +620,66 @@ def cpu_baseline(steps):
                       f"C=1 and C=2, 1 warm-up + median of {max(3, steps)} steps each ({t_all:.1f} s timed), "
                       f"torch CPU threads={threads} (this process's CPU share: affinity capped by the cgroup "
                       f"quota), cpu='{model_name}'"}
+
+
+def full_step_probes(args, info, tr, hr, value, step_ms):
+    """--full, on the timed trainer behind its timed steps: the idle-device host enqueue
+    time and (rank 0) the in-step rooflines; -> the keys they add to the result line."""
+    # host cost of enqueuing ONE step onto an idle device (queue empty): the
+    # back-to-back enqueue time of the timed loop includes waiting on a full hardware queue
+    idle = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        tr.step(hr)
+        idle.append(time.perf_counter() - t1)
+        torch.cuda.synchronize()
+    rec = {"host_enqueue_idle_ms_per_step": round(1000 * sorted(idle)[1], 3)}
+    if info.rank == 0:
+        roof, roof_f2 = fused_rooflines(tr, step_ms)
+        step_tf = value / info.world * TRAIN_GFLOP_PER_TILE_C2 / 1000.0
+        roof["step_mfma_tflops"] = round(step_tf, 1)
+        roof["step_mfma_frac"] = round(step_tf / PEAK_BF16_TFLOPS, 4)
+        rec.update(roofline=roof, roofline_f2=roof_f2, step_traffic=_pmc_step_total(step_ms))
+    return rec
+
+
+def full_extra_legs(args, info, dev, value):
+    """--full, on engines of their own (the timed trainer is gone by now): the one-rank
+    DP overhead, the isolated forward conv, C4 EDSR, C5 inference and the CPU baseline;
+    -> the keys they add to the result line (the other ranks only take part in the
+    collectives)."""
+    world = info.world
+    dp_probe = None
+    if world == 1 and not info.enabled and not args.no_dp_probe:
+        dp_probe = dp_overhead_probe(args)
+        _log(f"dp probe: {dp_probe}")
+    _log(f"timed: {value:.1f} tiles/s")
+    infer_dp = None
+    if world > 1 and not args.no_inference:  # every rank takes part (collectives)
+        infer_dp = inference_bench(dev, args.infer_region, args.infer_iters, 2 if args.no_rcab_infer else 0, info)
+        _log("multi-rank inference done")
+    if info.rank != 0:
+        return {}
+    roof_conv = conv_fwd_roofline(dev, args.batch)
+    _log("rooflines done")
+    edsr = None
+    if not args.no_edsr and world == 1:
+        edsr = edsr_bench(dev, args.edsr_batch, 10, 3)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        _log("edsr done")
+    infer = None
+    if not args.no_inference and world == 1:
+        infer = inference_bench(dev, args.infer_region, args.infer_iters, 2 if args.no_rcab_infer else 0)
+        _log("inference done")
+    if world > 1:
+        infer = infer_dp
+    cpu = None
+    if not args.no_cpu_baseline and world == 1:
+        cpu = cpu_baseline(args.cpu_steps)
+    return {"roofline_conv_fwd": roof_conv, "dp_overhead_1rank": dp_probe, "cpu_baseline": cpu, "inference": infer,
+            "edsr_x8": edsr}
 
 
 def main():
@@ -649,73 +747,30 @@ def main():
     tiles = B * world * args.steps
     value = tiles / dt
     step_ms = 1000 * dt / args.steps
-    # host cost of enqueuing ONE step onto an idle device (queue empty): the
-    # back-to-back enqueue time above includes waiting on a full hardware queue
-    idle = []
-    for _ in range(3):
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, tr, out)
+        _log(f"outputs written to {args.dump_outputs}")
+    rec = {
+        "metric": METRIC, "value": round(value, 2), "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3), "step_times": step_stats,
+        "ca_pass": bool(args.ca_pass), "du_pass": bool(args.du_pass),
+        "host_enqueue_ms_per_step": round(1000 * t_host / args.steps, 3), "micro": micro, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "rcan-10-20-64 train step (down4 + fwd + RMSE + interp RMSE + bwd + Adam), "
+                               f"{C}-var 48x48->192x192 tiles",
+                   "global_batch": B * world, "per_gpu_batch": B, "tile": "48->192",
+                   "parallelism": f"dp{world}"},
+        "model_tflops": round(value * TRAIN_GFLOP_PER_TILE_C2 / 1000.0, 1),
+        "loss": loss,
+    }
+    if args.full:
+        rec.update(full_step_probes(args, info, tr, hr, value, step_ms))
+    del tr, hr, out
+    if args.full:  # the extra lines run on their own engines
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        tr.step(hr)
-        idle.append(time.perf_counter() - t1)
-        torch.cuda.synchronize()
-    host_idle_ms = 1000 * sorted(idle)[1]
+        torch.cuda.empty_cache()
+        rec.update(full_extra_legs(args, info, dev, value))
     if info.rank == 0:
-        roof, roof_f2 = fused_rooflines(tr, step_ms)
-        step_tf = value / world * TRAIN_GFLOP_PER_TILE_C2 / 1000.0
-        roof["step_mfma_tflops"] = round(step_tf, 1)
-        roof["step_mfma_frac"] = round(step_tf / PEAK_BF16_TFLOPS, 4)
-    del tr, hr  # the extra lines below run on their own engines
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    dp_probe = None
-    if world == 1 and not info.enabled and not args.no_dp_probe:
-        dp_probe = dp_overhead_probe(args)
-        _log(f"dp probe: {dp_probe}")
-    _log(f"timed: {value:.1f} tiles/s")
-    infer_dp = None
-    if world > 1 and not args.no_inference:  # every rank takes part (collectives)
-        infer_dp = inference_bench(dev, args.infer_region, args.infer_iters, 2 if args.no_rcab_infer else 0, info)
-        _log("multi-rank inference done")
-    if info.rank == 0:
-        roof_conv = conv_fwd_roofline(dev, B)
-        _log("rooflines done")
-        edsr = None
-        if not args.no_edsr and world == 1:
-            edsr = edsr_bench(dev, args.edsr_batch, 10, 3)
-            torch.cuda.synchronize()
-            torch.cuda.empty_cache()
-            _log("edsr done")
-        infer = None
-        if not args.no_inference and world == 1:
-            infer = inference_bench(dev, args.infer_region, args.infer_iters, 2 if args.no_rcab_infer else 0)
-            _log("inference done")
-        if world > 1:
-            infer = infer_dp
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(args.cpu_steps)
-        rec = {
-            "metric": METRIC, "value": round(value, 2), "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3), "step_times": step_stats,
-            "ca_pass": bool(args.ca_pass), "du_pass": bool(args.du_pass),
-            "host_enqueue_ms_per_step": round(1000 * t_host / args.steps, 3),
-            "host_enqueue_idle_ms_per_step": round(host_idle_ms, 3), "micro": micro, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "rcan-10-20-64 train step (down4 + fwd + RMSE + interp RMSE + bwd + Adam), "
-                                   f"{C}-var 48x48->192x192 tiles",
-                       "global_batch": B * world, "per_gpu_batch": B, "tile": "48->192",
-                       "parallelism": f"dp{world}"},
-            "model_tflops": round(value * TRAIN_GFLOP_PER_TILE_C2 / 1000.0, 1),
-            "loss": loss,
-            "roofline": roof,
-            "roofline_f2": roof_f2,
-            "step_traffic": _pmc_step_total(step_ms),
-            "roofline_conv_fwd": roof_conv,
-            "dp_overhead_1rank": dp_probe,
-            "cpu_baseline": cpu,
-            "inference": infer,
-            "edsr_x8": edsr,
-        }
         print(json.dumps(rec), flush=True)
     if info.enabled:
         torch.distributed.destroy_process_group()

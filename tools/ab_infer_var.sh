@@ -7,7 +7,7 @@ REPS=${REPS:-2}
 for rep in $(seq $REPS); do
   for v in "$@"; do
     IFS=: read -r name lib flags envs <<< "$v"
-    env ${envs//,/ } SRMI_LIB=${lib:+$R/$lib} timeout -k 10 200 python bench.py --no-train --no-edsr --infer-iters 10 $flags \
+    env ${envs//,/ } SRMI_LIB=${lib:+$R/$lib} timeout -k 10 200 python bench.py --full --no-train --no-edsr --infer-iters 10 $flags \
       > $O/abiv.json 2>> $O/abiv.err || { echo "variant $name failed"; exit 2; }
     python -c "
 import json; d=json.loads(open('$O/abiv.json').read().strip().splitlines()[-1])['inference']

@@ -7,7 +7,7 @@ REPS=${REPS:-2}
 for rep in $(seq $REPS); do
   for v in "$@"; do
     IFS=: read -r name lib flags envs <<< "$v"
-    env ${envs//,/ } SRMI_LIB=${lib:+$R/$lib} timeout -k 10 200 python bench.py --no-cpu-baseline --no-inference --no-edsr --no-dp-probe \
+    env ${envs//,/ } SRMI_LIB=${lib:+$R/$lib} timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-inference --no-edsr --no-dp-probe \
       --steps 20 --warmup 3 $flags > $O/abv.json 2>> $O/abv.err || { echo "variant $name failed"; exit 2; }
     python -c "
 import json; d=json.loads(open('$O/abv.json').read().strip().splitlines()[-1])
