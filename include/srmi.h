@@ -158,6 +158,29 @@ int srmi_backward_stages(srmi_engine* e, const float* params, const float* lr, c
  * 0 if as a launch of its own (SRMI_FLAG_DU_PASS, exact fp32, unfusable shapes). */
 int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
 
+/* diagnostic (tests): device address, element count and element size of one of the
+ * engine's saved maps, valid until the next forward / backward call on this engine.
+ * Maps are [batch][lr_h][lr_w][64] (the first n images of the last forward are
+ * meaningful), element size 4 for the fp32 maps and the exact-fp32 engine's, 2 (bf16)
+ * else; the CA records are fp32 [batch][160] / [batch][224].  g = residual group,
+ * b = RCAB 1 .. nblocks (HB: b = 0 .. nblocks, the input of RCAB b + 1; HB(nlayers, 0)
+ * is the body tail's input); EDSR: g = resblock, b = 0 (HB) / 1 (T).  GROUP_IN_GRAD(g)
+ * is the fp32 gradient w.r.t. group g's input, where the backward stage of group g
+ * leaves it (the engine alternates two buffers; the accessor resolves which).  A
+ * buffer this engine does not have (an inference engine's backward maps or per-RCAB
+ * slots, EDSR's CA state), or g / b out of range: SRMI_ERR_ARG. */
+#define SRMI_BUF_X0F 0
+#define SRMI_BUF_HB 1
+#define SRMI_BUF_T 2
+#define SRMI_BUF_U 3
+#define SRMI_BUF_REC 4
+#define SRMI_BUF_BREC 5
+#define SRMI_BUF_DU 6
+#define SRMI_BUF_DZ 7
+#define SRMI_BUF_DRESF 8
+#define SRMI_BUF_GROUP_IN_GRAD 9
+int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size_t* elems, int* elem_bytes);
+
 /* RMSE (l2loss, squared=False).  loss4[0] = sum of squares (this rank),
  * loss4[1] = global element count; after the optional all-reduce of loss4[0],
  * srmi_rmse_finalize sets loss4[3] = L = sqrt(S/count), loss4[2] = 1/(count L). */

@@ -1086,6 +1086,65 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
   return 0;
 }
 
+int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size_t* elems, int* elem_bytes) {
+  if (!e || !ptr || !elems || !elem_bytes) return SRMI_ERR_ARG;
+  const bool rcan = e->P.cfg.arch == SRMI_ARCH_RCAN;
+  const int nl = e->P.cfg.nlayers, nb = e->nbe();
+  void* p = nullptr;
+  size_t n = e->mapn;
+  int eb = (int)e->esz;
+  switch (which) {
+    case SRMI_BUF_X0F:
+      p = e->X0f;
+      eb = 4;
+      break;
+    case SRMI_BUF_HB:  // (inference engines rotate three slots: no per-block map)
+      if (!e->train || g < 0 || g > nl || b < 0 || b > (rcan && g < nl ? nb : 0)) return SRMI_ERR_ARG;
+      p = e->hb(g, b);
+      break;
+    case SRMI_BUF_T:
+      if (!e->train || g < 0 || g >= nl || b < 1 || b > nb) return SRMI_ERR_ARG;
+      p = e->Tm(g, b);
+      break;
+    case SRMI_BUF_U:
+      if (!e->train || !rcan || g < 0 || g >= nl || b < 1 || b > nb) return SRMI_ERR_ARG;
+      p = e->Um(g, b);
+      break;
+    case SRMI_BUF_REC:
+    case SRMI_BUF_BREC:
+      if (!e->train || !rcan || g < 0 || g >= nl || b < 1 || b > nb) return SRMI_ERR_ARG;
+      p = which == SRMI_BUF_REC ? e->recp(g, b) : e->brecp(g, b);
+      n = (size_t)e->N * (which == SRMI_BUF_REC ? 160 : 224);
+      eb = 4;
+      break;
+    case SRMI_BUF_DU:  // (EDSR has no du)
+      if (!e->train || !rcan) return SRMI_ERR_ARG;
+      p = e->DU;
+      break;
+    case SRMI_BUF_DZ:
+      if (!e->train) return SRMI_ERR_ARG;
+      p = e->DZ;
+      break;
+    case SRMI_BUF_DRESF:
+      if (!e->train) return SRMI_ERR_ARG;
+      p = e->dRESf;
+      eb = 4;
+      break;
+    case SRMI_BUF_GROUP_IN_GRAD:  // backward_impl's ghf of group g (its streams swap after every group)
+      if (!e->train || !rcan || g < 0 || g >= nl) return SRMI_ERR_ARG;
+      p = ((nl - 1 - g) & 1) ? e->GAf : e->GBf;
+      eb = 4;
+      break;
+    default:
+      return SRMI_ERR_ARG;
+  }
+  if (!p) return SRMI_ERR_ARG;
+  *ptr = p;
+  *elems = n;
+  *elem_bytes = eb;
+  return 0;
+}
+
 int srmi_rmse_partial(srmi_engine* e, const float* pred, const float* target, size_t n, double count_global,
                       float* loss4, void* stream) {
   if (!e || !pred || !target || !loss4) return SRMI_ERR_ARG;

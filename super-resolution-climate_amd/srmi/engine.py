@@ -141,7 +141,27 @@ class Engine:
             out = torch.empty((n, self.spec.nchannels_out, self.hr_h, self.hr_w), dtype=torch.float32,
                               device=self.device)
         call("srmi_forward", self._h, ptr(params), ptr(lr), ptr(out), n, stream_handle(stream))
+        self._last_n = n
         return out
+
+    def buffer(self, name: str, g: int = 0, b: int = 0) -> torch.Tensor:
+        """Diagnostic (tests): one of the engine's saved maps as a view into the workspace
+        (no copy; srmi_engine_buffer), valid until the next forward / backward.  name:
+        a key of _lib.BUFFERS.  Maps come as [n, h, w, 64] (n = the last forward's tiles)
+        in the map's own type, the CA records REC / BREC as [n, 160] / [n, 224] fp32."""
+        if name not in _lib.BUFFERS:
+            raise _lib.SrmiError(f"unknown engine buffer {name!r} ({' | '.join(_lib.BUFFERS)})")
+        p, elems, eb = C.c_void_p(), C.c_size_t(), C.c_int()
+        call("srmi_engine_buffer", self._h, _lib.BUFFERS[name], int(g), int(b), C.byref(p), C.byref(elems),
+             C.byref(eb))
+        off = int(p.value) - self.workspace.data_ptr()
+        nbytes = int(elems.value) * eb.value
+        if off < 0 or off + nbytes > self.workspace.numel():
+            raise _lib.SrmiError(f"engine buffer {name} lies outside the workspace")
+        flat = self.workspace[off:off + nbytes].view(torch.float32 if eb.value == 4 else torch.bfloat16)
+        n = getattr(self, "_last_n", self.batch)
+        per = int(elems.value) // self.batch
+        return flat.view(self.batch, *((self.lr_h, self.lr_w, 64) if name not in ("REC", "BREC") else (per,)))[:n]
 
     def rmse_partial(self, pred: torch.Tensor, target: torch.Tensor, loss4: torch.Tensor, count_global: float,
                      stream=None):

@@ -26,6 +26,71 @@ def test_library_exports_every_header_symbol():
     assert lib.srmi_version() >= 100
 
 
+def test_engine_buffer_addresses_lie_in_the_workspace_and_do_not_overlap():
+    """srmi_engine_buffer on an engine carved over a host buffer (nothing is launched):
+    every map it reports lies inside the workspace, no two overlap, GROUP_IN_GRAD
+    alternates between two buffers from the last group down, and what the engine does
+    not have is SRMI_ERR_ARG."""
+    import ctypes as C
+    from srmi import _lib
+    from srmi.engine import NetSpec
+    lib = _lib.load()
+    nl, nb, N, h, w = 3, 2, 2, 8, 32
+
+    def make(spec, train):
+        cfg = spec.cstruct(N, h, w)
+        nbytes = C.c_size_t()
+        assert lib.srmi_workspace_size(C.byref(cfg), train, C.byref(nbytes)) == 0
+        ws = (C.c_char * (nbytes.value + 256))()
+        eng = C.c_void_p()
+        assert lib.srmi_engine_create(C.byref(cfg), ws, len(ws), train, C.byref(eng)) == 0
+        return eng, ws
+
+    def buf(eng, name, g=0, b=0):
+        p, n, eb = C.c_void_p(), C.c_size_t(), C.c_int()
+        rc = lib.srmi_engine_buffer(eng, _lib.BUFFERS[name], g, b, C.byref(p), C.byref(n), C.byref(eb))
+        return rc, p.value, n.value * eb.value, eb.value
+
+    for dtype, esz in (("fp32", 4), ("bf16", 2)):
+        spec = NetSpec(arch="rcan", nchannels_in=2, nchannels_out=2, nlayers=nl, nblocks=nb, scale=4, dtype=dtype)
+        eng, ws = make(spec, 1)
+        base = C.addressof(ws)
+        want = [("X0F", 0, 0), ("DU", 0, 0), ("DZ", 0, 0), ("DRESF", 0, 0), ("HB", nl, 0),
+                ("GROUP_IN_GRAD", nl - 1, 0), ("GROUP_IN_GRAD", nl - 2, 0)]
+        want += [("HB", g, b) for g in range(nl) for b in range(nb + 1)]
+        want += [(k, g, b) for k in ("T", "U", "REC", "BREC") for g in range(nl) for b in range(1, nb + 1)]
+        spans = []
+        for name, g, b in want:
+            rc, p, nbytes, eb = buf(eng, name, g, b)
+            assert rc == 0, (name, g, b)
+            assert eb == (4 if name in ("X0F", "DRESF", "GROUP_IN_GRAD", "REC", "BREC") else esz), name
+            assert nbytes == (N * {"REC": 160, "BREC": 224}[name] * 4 if name in ("REC", "BREC") else N * h * w * 64 * eb)
+            assert base <= p and p + nbytes <= base + len(ws), (name, g, b)
+            spans.append((p, p + nbytes, (name, g, b)))
+        spans.sort()
+        for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
+            assert a1 <= b0, (ka, kb)
+        assert buf(eng, "GROUP_IN_GRAD", 0)[1] == buf(eng, "GROUP_IN_GRAD", 2)[1] != buf(eng, "GROUP_IN_GRAD", 1)[1]
+        for name, g, b in (("HB", nl + 1, 0), ("HB", nl, 1), ("HB", 0, nb + 1), ("T", 0, 0), ("U", 0, nb + 1),
+                           ("REC", nl, 1), ("BREC", -1, 1), ("GROUP_IN_GRAD", nl, 0)):
+            assert buf(eng, name, g, b)[0] == -10001, (name, g, b)
+        p, n, eb = C.c_void_p(), C.c_size_t(), C.c_int()
+        assert lib.srmi_engine_buffer(eng, 99, 0, 0, C.byref(p), C.byref(n), C.byref(eb)) == -10001
+        assert lib.srmi_engine_buffer(None, 0, 0, 0, C.byref(p), C.byref(n), C.byref(eb)) == -10001
+        lib.srmi_engine_destroy(eng)
+        inf, ws = make(spec, 0)  # an inference engine keeps no per-block maps and has no backward
+        assert buf(inf, "X0F")[0] == 0
+        for name in ("HB", "T", "U", "REC", "BREC", "DU", "DZ", "DRESF", "GROUP_IN_GRAD"):
+            assert buf(inf, name, 0, 1 if name in ("T", "U", "REC", "BREC") else 0)[0] == -10001, name
+        lib.srmi_engine_destroy(inf)
+    edsr, ws = make(NetSpec(arch="edsr", nchannels_in=2, nchannels_out=2, nlayers=nl, scale=4, dtype="fp32"), 1)
+    assert buf(edsr, "HB", nl, 0)[0] == 0 and buf(edsr, "T", nl - 1, 1)[0] == 0 and buf(edsr, "DZ")[0] == 0
+    for name, g, b in (("U", 0, 1), ("REC", 0, 1), ("BREC", 0, 1), ("DU", 0, 0), ("GROUP_IN_GRAD", 0, 0), ("HB", 0, 1),
+                       ("T", nl, 1)):
+        assert buf(edsr, name, g, b)[0] == -10001, (name, g, b)
+    lib.srmi_engine_destroy(edsr)
+
+
 @pytest.mark.parametrize("C", [1, 2])
 def test_native_param_plan_matches_reference_state_dict(C):
     from srmi.engine import NetSpec, param_table
