@@ -155,7 +155,13 @@ int srmi_backward_stages(srmi_engine* e, const float* params, const float* lr, c
  * inference engine's one-launch RCAB (0, 2) on the buffers of the last forward;
  * which = 4 (nothing launched, reps ignored): 1 if the engine's backward runs the CA
  * backward inside the fused conv2 backward (du formed from the bf16 gradient stream),
- * 0 if as a launch of its own (SRMI_FLAG_DU_PASS, exact fp32, unfusable shapes). */
+ * 0 if as a launch of its own (SRMI_FLAG_DU_PASS, exact fp32, unfusable shapes);
+ * which = 5 / 6 (nothing launched): the row chunks per image of the filter gradient
+ * beside conv1's dgrad (F1, and the group tail's) / beside conv2's dgrad (F2) at the last
+ * forward's n -- the partial slabs of such a launch are one per (image, row chunk,
+ * 48-column block); which = 7 (nothing launched): bit 0 the RCAB backward's dgrad and
+ * filter gradient run as one fused launch, bit 1 the RCAB filter gradients' partial
+ * slabs are bf16, bit 2 = which 4. */
 int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
 
 /* diagnostic (tests): device address, element count and element size of one of the
@@ -180,6 +186,33 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
 #define SRMI_BUF_DRESF 8
 #define SRMI_BUF_GROUP_IN_GRAD 9
 int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size_t* elems, int* elem_bytes);
+
+/* diagnostic (tests): trace of the RCAN backward's in-group state, which every RCAB of a
+ * residual group rewrites in place.  With a buffer set (256-byte aligned, at least
+ * srmi_engine_trace_size bytes, the caller's; NULL = off, the default), the backward
+ * enqueues asynchronous device-to-device copies on its own stream, between its launches
+ * (no kernel, no synchronisation; no launch, operand or order changes), into the slot
+ * (which, g, b) at srmi_engine_trace_slot's byte offset:
+ *   GRB    (b = 0): the bf16 copy of group g's output gradient at the start of its stage
+ *          (the group tail's dgrad and filter-gradient operand);
+ *   STREAM (b = 0 .. nblocks): the in-group gradient stream w.r.t. RCAB b's output, in the
+ *          engine's operand type -- b = nblocks after the group tail's launch, b - 1 after
+ *          RCAB b's conv1 backward (b = 0: the bf16 copy of the group input gradient);
+ *   PACC   (b = 1 .. nblocks): fp32 [batch][nstrips][128], the CA sums (sum g | sum g u per
+ *          strip) of RCAB b, copied at the same points as STREAM b;
+ *   DZ     (b = 1 .. nblocks): after RCAB b's conv2 backward;
+ *   DU     (b = 1 .. nblocks): copied only where the engine writes du to memory
+ *          (srmi_engine_probe which = 4 returns 0).
+ * Maps are [batch][lr_h][lr_w][64]; the first n images are copied.  Not while a staged
+ * backward is half-way through (SRMI_ERR_ARG); RCAN train engines only. */
+#define SRMI_TRACE_GRB 0
+#define SRMI_TRACE_STREAM 1
+#define SRMI_TRACE_PACC 2
+#define SRMI_TRACE_DZ 3
+#define SRMI_TRACE_DU 4
+int srmi_engine_trace_size(srmi_engine* e, size_t* bytes);
+int srmi_engine_trace(srmi_engine* e, void* buf, size_t bytes);
+int srmi_engine_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offset, size_t* elems, int* elem_bytes);
 
 /* RMSE (l2loss, squared=False).  loss4[0] = sum of squares (this rank),
  * loss4[1] = global element count; after the optional all-reduce of loss4[0],

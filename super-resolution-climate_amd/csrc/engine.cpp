@@ -236,6 +236,9 @@ struct srmi_engine {
   // from one stage to the next, so a skipped, repeated or reordered stage is refused
   int next_stage = 0;
   const float* probe_prm = nullptr;  // the parameters of the last backward / inference forward (srmi_engine_probe)
+  // diagnostic (srmi_engine_trace): the caller's buffer the RCAN backward copies its in-group
+  // state into, one region per residual group; null = off (one branch per copy site)
+  char* trace = nullptr;
 
   bf16_t* at(bf16_t* base, size_t elems) const {
     return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(base) + elems * esz);
@@ -553,6 +556,50 @@ static int dgrad_with_wgrad(srmi_engine* e, const ConvParams& cp, int epi, const
   return conv3x3_launch(cp, epi, st);
 }
 
+// ---- the backward trace (srmi_engine_trace): layout of the caller's buffer.  Per residual
+// group g, 256-byte aligned pieces in this order: GRB | STREAM b = 0 .. nb | PACC b = 1 .. nb |
+// DZ b = 1 .. nb | DU b = 1 .. nb; maps are [N][h][w][64] of the engine's operand type (capacity
+// N: the first n images are copied), PACC is fp32 [N][nstrips][128].
+static size_t trace_map_bytes(const srmi_engine* e) { return (e->mapn * e->esz + 255) & ~(size_t)255; }
+static size_t trace_pacc_bytes(const srmi_engine* e) {
+  return ((size_t)e->N * conv3x3_nstrips(e->h, e->w) * 128 * sizeof(float) + 255) & ~(size_t)255;
+}
+static size_t trace_group_bytes(const srmi_engine* e) {
+  const size_t nb = (size_t)e->P.cfg.nblocks;
+  return trace_map_bytes(e) * (3 * nb + 2) + trace_pacc_bytes(e) * nb;
+}
+static size_t trace_bytes(const srmi_engine* e) { return trace_group_bytes(e) * (size_t)e->P.cfg.nlayers; }
+// byte offset of slot (which, g, b), or (size_t)-1 if there is no such slot
+static size_t trace_offset(const srmi_engine* e, int which, int g, int b) {
+  const int nl = e->P.cfg.nlayers, nb = e->P.cfg.nblocks;
+  if (g < 0 || g >= nl) return (size_t)-1;
+  const size_t m = trace_map_bytes(e), pa = trace_pacc_bytes(e), base = trace_group_bytes(e) * (size_t)g;
+  switch (which) {
+    case SRMI_TRACE_GRB:
+      return b == 0 ? base : (size_t)-1;
+    case SRMI_TRACE_STREAM:
+      return b >= 0 && b <= nb ? base + m * (size_t)(1 + b) : (size_t)-1;
+    case SRMI_TRACE_PACC:
+      return b >= 1 && b <= nb ? base + m * (size_t)(nb + 2) + pa * (size_t)(b - 1) : (size_t)-1;
+    case SRMI_TRACE_DZ:
+      return b >= 1 && b <= nb ? base + m * (size_t)(nb + 2) + pa * (size_t)nb + m * (size_t)(b - 1) : (size_t)-1;
+    case SRMI_TRACE_DU:
+      return b >= 1 && b <= nb ? base + m * (size_t)(2 * nb + 2) + pa * (size_t)nb + m * (size_t)(b - 1)
+                               : (size_t)-1;
+    default:
+      return (size_t)-1;
+  }
+}
+// one async device-to-device copy of the first n images' share of src into the slot
+static int trace_copy(const srmi_engine* e, int which, int g, int b, const void* src, int n, hipStream_t st) {
+  const size_t off = trace_offset(e, which, g, b);
+  if (off == (size_t)-1) return SRMI_ERR_ARG;
+  const size_t bytes = which == SRMI_TRACE_PACC ? (size_t)n * conv3x3_nstrips(e->h, e->w) * 128 * sizeof(float)
+                                                : (size_t)n * e->h * e->w * 64 * e->esz;
+  const hipError_t err = hipMemcpyAsync(e->trace + off, src, bytes, hipMemcpyDeviceToDevice, st);
+  return err == hipSuccess ? 0 : -(int)err;
+}
+
 // SRMI_TRACE_ERRORS=1 in the environment: every failing step prints its line
 static int trace_rc(int rc, int line) {
   static const bool on = std::getenv("SRMI_TRACE_ERRORS") != nullptr;
@@ -794,6 +841,9 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
       ghb = sw ? e->GAb : e->GBb;
       if (stage < s_lo || stage > s_hi) continue;
       const ConvRef& gt = P.group_tail[g];
+      // (srmi_engine_trace: the in-group stream in the engine's operand type)
+      const void* gstream = g16 ? static_cast<const void*>(ghb) : ghf;
+      if (e->trace) RC(trace_copy(e, SRMI_TRACE_GRB, g, 0, gRb, n, st));
       // the filter-gradient reductions: collected for one launch at the group's end (or, with
       // the CA backward's MLP as a launch of its own (SRMI_F2_MLP 0), riding in that launch)
       ReduceSet prev2{}, prev1{};
@@ -825,6 +875,10 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
           RC(conv_wgrad(e, gt, e->hb(g, nb), gRb, n, h, w, grads, true, 1.f, st));
           RC(conv3x3_launch(cp, epi, st));
         }
+      }
+      if (e->trace) {
+        RC(trace_copy(e, SRMI_TRACE_STREAM, g, nb, gstream, n, st));
+        RC(trace_copy(e, SRMI_TRACE_PACC, g, nb, e->pacc, n, st));
       }
       for (int b = nb; b >= 1; --b) {
         const RCABRef& r = P.groups[g][b - 1];
@@ -866,6 +920,10 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
           have_prev = false;
         }
         RC(dgrad_with_wgrad(e, cp, epi, wp, 2, st));
+        if (e->trace) {
+          RC(trace_copy(e, SRMI_TRACE_DZ, g, b, dz, n, st));
+          if (!du_fused) RC(trace_copy(e, SRMI_TRACE_DU, g, b, du, n, st));
+        }
         const bool last = (b == 1);
         epi = EPI_DG_ACC;
         // g += dgrad(dz): in the group's first RCAB into the group input gradient (fp32 +
@@ -881,6 +939,10 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
         RC(wgrad_params(e, r.c1, e->hb(g, b - 1), dz, n, h, w, grads, true, 1.f, rs1, e->slab_r(b, 1),
                         e->bslab_r(b, 1), e->slab_r_floats, e->bslab_r_floats, &wp, &red1, kSlab16));
         RC(dgrad_with_wgrad(e, cp, epi, wp, 1, st));
+        if (e->trace) {
+          RC(trace_copy(e, SRMI_TRACE_STREAM, g, b - 1, gstream, n, st));
+          if (!last) RC(trace_copy(e, SRMI_TRACE_PACC, g, b - 1, e->pacc, n, st));
+        }
         prev2 = red2;
         prev1 = red1;
         have_prev = true;
@@ -1032,7 +1094,11 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
                            e->recp(0, 2), S_(stream)));
     return 0;
   }
-  if (which == 4) {  // does the backward form du inside the fused conv2 backward (1) or not (0)
+  if (which == 5 || which == 6) {  // the filter gradients' row chunks per image of F1 (5) / F2 (6)
+    if (!e || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN || e->last_n < 1) return SRMI_ERR_ARG;
+    return rcab_row_splits(e, e->last_n, which == 5 ? 1 : 2);
+  }
+  if (which == 4 || which == 7) {  // 4: does the backward form du inside the fused conv2 backward (1) or not (0)
     if (!e || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN || e->last_n < 1 || !e->probe_prm) return SRMI_ERR_ARG;
     const int n = e->last_n, b = e->P.cfg.nblocks >= 2 ? 2 : 1;
     const RCABRef& r = e->P.groups[0][b - 1];
@@ -1043,6 +1109,8 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
     ReduceSet red;
     RC(wgrad_params(e, r.c2, e->Tm(0, b), e->DU, n, e->h, e->w, e->slab, false, 1.f, rcab_row_splits(e, n, 2),
                     e->slab_r(b, 0), e->bslab_r(b, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red, kSlab16));
+    if (which == 7)  // how the RCAB backward launches run: fused | bf16 partial slabs | du formed in F2
+      return (rcab_bwd_fusable(cp, wp) ? 1 : 0) | (wp.slab16 ? 2 : 0) | (du_in_f2(e, cp, wp, epi) ? 4 : 0);
     return du_in_f2(e, cp, wp, epi) ? 1 : 0;
   }
   if (!e || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN || e->last_n < 1 || reps < 1) return SRMI_ERR_ARG;
@@ -1142,6 +1210,30 @@ int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size
   *ptr = p;
   *elems = n;
   *elem_bytes = eb;
+  return 0;
+}
+
+int srmi_engine_trace_size(srmi_engine* e, size_t* bytes) {
+  if (!e || !bytes || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN) return SRMI_ERR_ARG;
+  *bytes = trace_bytes(e);
+  return 0;
+}
+
+int srmi_engine_trace(srmi_engine* e, void* buf, size_t bytes) {
+  if (!e || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN) return SRMI_ERR_ARG;
+  if (e->next_stage != 0) return SRMI_ERR_ARG;  // not half-way through a staged backward
+  if (buf && (bytes < trace_bytes(e) || ((uintptr_t)buf & 255))) return SRMI_ERR_WORKSPACE;
+  e->trace = static_cast<char*>(buf);
+  return 0;
+}
+
+int srmi_engine_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offset, size_t* elems, int* elem_bytes) {
+  if (!e || !offset || !elems || !elem_bytes || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN) return SRMI_ERR_ARG;
+  const size_t off = trace_offset(e, which, g, b);
+  if (off == (size_t)-1) return SRMI_ERR_ARG;
+  *offset = off;
+  *elems = which == SRMI_TRACE_PACC ? (size_t)e->N * conv3x3_nstrips(e->h, e->w) * 128 : e->mapn;
+  *elem_bytes = which == SRMI_TRACE_PACC ? 4 : (int)e->esz;
   return 0;
 }
 

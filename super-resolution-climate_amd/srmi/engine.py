@@ -163,6 +163,46 @@ class Engine:
         per = int(elems.value) // self.batch
         return flat.view(self.batch, *((self.lr_h, self.lr_w, 64) if name not in ("REC", "BREC") else (per,)))[:n]
 
+    def trace(self, on: bool = True) -> Optional[torch.Tensor]:
+        """Diagnostic (tests): turn the backward trace on (a buffer of srmi_engine_trace_size
+        bytes, owned by this object and returned) or off (srmi_engine_trace).  While on, every
+        residual group's backward stage copies its in-group state into the buffer (async
+        copies on the backward's stream); trace_view reads a slot."""
+        if not on:
+            call("srmi_engine_trace", self._h, None, 0)
+            self._trace = None
+            return None
+        nbytes = C.c_size_t()
+        call("srmi_engine_trace_size", self._h, C.byref(nbytes))
+        buf = torch.zeros(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        call("srmi_engine_trace", self._h, ptr(buf), buf.numel())
+        self._trace = buf
+        return buf
+
+    def trace_view(self, name: str, g: int = 0, b: int = 0) -> torch.Tensor:
+        """One slot of the trace buffer as a view (no copy), shaped as buffer() shapes the
+        engine's maps: GRB / STREAM / DZ / DU [n, h, w, 64] in the engine's operand type,
+        PACC [n, nstrips, 128] fp32.  name: a key of _lib.TRACE_SLOTS."""
+        if getattr(self, "_trace", None) is None:
+            raise _lib.SrmiError("the backward trace is off (Engine.trace())")
+        if name not in _lib.TRACE_SLOTS:
+            raise _lib.SrmiError(f"unknown trace slot {name!r} ({' | '.join(_lib.TRACE_SLOTS)})")
+        off, elems, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        call("srmi_engine_trace_slot", self._h, _lib.TRACE_SLOTS[name], int(g), int(b), C.byref(off), C.byref(elems),
+             C.byref(eb))
+        nbytes = int(elems.value) * eb.value
+        if off.value + nbytes > self._trace.numel():
+            raise _lib.SrmiError(f"trace slot {name} lies outside the trace buffer")
+        flat = self._trace[off.value:off.value + nbytes].view(torch.float32 if eb.value == 4 else torch.bfloat16)
+        n = getattr(self, "_last_n", self.batch)
+        shape = (self.lr_h, self.lr_w, 64) if name != "PACC" else (int(elems.value) // self.batch // 128, 128)
+        return flat.view(self.batch, *shape)[:n]
+
+    def probe(self, which: int, reps: int = 1, stream=None) -> int:
+        """srmi_engine_probe: which = 4 du formed inside F2; 5 / 6 the filter gradients' row
+        chunks per image in F1 / F2; 7 bit 0 fused launches, bit 1 bf16 partial slabs, bit 2 = 4."""
+        return call("srmi_engine_probe", self._h, int(which), int(reps), stream_handle(stream))
+
     def rmse_partial(self, pred: torch.Tensor, target: torch.Tensor, loss4: torch.Tensor, count_global: float,
                      stream=None):
         call("srmi_rmse_partial", self._h, ptr(pred), ptr(target), pred.numel(), float(count_global), ptr(loss4),

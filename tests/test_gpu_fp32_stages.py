@@ -241,3 +241,54 @@ def test_engine_buffer_refuses_what_the_engine_lacks():
     bf = Engine(NetSpec(arch="rcan", nchannels_in=1, nchannels_out=1, nlayers=1, nblocks=1, scale=4), 1, (48, 48),
                 train=True, device=d)
     assert bf.buffer("T", 0, 1).dtype == torch.bfloat16 and bf.buffer("X0F").dtype == torch.float32
+    # the backward trace: off by default and refused where there is nothing to trace
+    with pytest.raises(SrmiError):
+        tr.trace_view("DZ", 0, 1)
+    for other in (inf, ed):
+        with pytest.raises(SrmiError):
+            other.trace(True)
+    tr.trace(True)
+    assert tr.trace_view("STREAM", 1, 0).shape == (2, 8, 32, 64) and tr.trace_view("DZ", 0, 2).dtype == torch.float32
+    assert tr.trace_view("PACC", 0, 1).shape[0] == 2 and tr.trace_view("PACC", 0, 1).shape[2] == 128
+    assert bf.trace(True) is not None and bf.trace_view("GRB", 0, 0).dtype == torch.bfloat16
+    for name, g, b in (("GRB", 0, 1), ("GRB", 2, 0), ("STREAM", 0, 3), ("STREAM", 0, -1), ("PACC", 0, 0), ("DZ", 0, 3),
+                       ("DU", -1, 1), ("DU", 0, 0)):
+        with pytest.raises(SrmiError):
+            tr.trace_view(name, g, b)
+    with pytest.raises(SrmiError):
+        tr.trace_view("NOPE")
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_trace_off_leaves_the_backward_bit_identical(dtype):
+    """One step with the trace on, then one without on the same engine, and a fresh engine
+    that never had one: the same outputs and gradients bit for bit (the trace adds copies
+    between the launches and changes no launch); with it off nothing is written to the buffer."""
+    import dataclasses
+    from srmi.engine import Engine
+    case = _case((48, 48), 16, 2, 3)
+    spec = dataclasses.replace(case["spec"], dtype=dtype)
+    d = dev()
+    lr, dy, flat = case["lr"].to(d), case["dy"].to(d), case["flat"].to(d)
+
+    def step(eng):
+        out = eng.forward(flat, lr)
+        grads = torch.zeros(eng.n_params, device=d)
+        eng.backward(flat, lr, grads, dy=dy)
+        torch.cuda.synchronize()
+        return out.clone(), grads
+
+    eng = Engine(spec, case["B"], (48, 48), train=True, device=d)
+    eng.pack(flat)
+    buf = eng.trace(True)
+    traced = step(eng)
+    assert bool(buf.any())
+    eng.trace(False)
+    buf.zero_()
+    plain = step(eng)
+    assert not bool(buf.any())
+    fresh = Engine(spec, case["B"], (48, 48), train=True, device=d)
+    fresh.pack(flat)
+    never = step(fresh)
+    for a, b in ((traced, never), (plain, never)):
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])

@@ -91,6 +91,71 @@ def test_engine_buffer_addresses_lie_in_the_workspace_and_do_not_overlap():
     lib.srmi_engine_destroy(edsr)
 
 
+def test_trace_slots_tile_the_trace_buffer_without_overlap():
+    """srmi_engine_trace_size / _trace / _trace_slot on engines carved over host buffers
+    (nothing is launched): every slot lies inside the reported size, no two overlap, a short
+    or misaligned buffer and engines with no RCAN backward are refused, NULL turns it off."""
+    import ctypes as C
+    from srmi import _lib
+    from srmi.engine import NetSpec
+    lib = _lib.load()
+    nl, nb, N, h, w = 2, 3, 3, 8, 48
+
+    def make(spec, train):
+        cfg = spec.cstruct(N, h, w)
+        nbytes = C.c_size_t()
+        assert lib.srmi_workspace_size(C.byref(cfg), train, C.byref(nbytes)) == 0
+        ws = (C.c_char * (nbytes.value + 256))()
+        eng = C.c_void_p()
+        assert lib.srmi_engine_create(C.byref(cfg), ws, len(ws), train, C.byref(eng)) == 0
+        return eng, ws
+
+    def slot(eng, name, g, b):
+        off, n, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        rc = lib.srmi_engine_trace_slot(eng, _lib.TRACE_SLOTS[name], g, b, C.byref(off), C.byref(n), C.byref(eb))
+        return rc, off.value, n.value * eb.value, eb.value
+
+    nstrips = lib.srmi_conv3x3_nstrips(h, w)
+    for dtype, esz in (("fp32", 4), ("bf16", 2)):
+        spec = NetSpec(arch="rcan", nchannels_in=1, nchannels_out=1, nlayers=nl, nblocks=nb, scale=4, dtype=dtype)
+        eng, ws = make(spec, 1)
+        total = C.c_size_t()
+        assert lib.srmi_engine_trace_size(eng, C.byref(total)) == 0
+        want = [("GRB", g, 0) for g in range(nl)] + [("STREAM", g, b) for g in range(nl) for b in range(nb + 1)]
+        want += [(k, g, b) for k in ("PACC", "DZ", "DU") for g in range(nl) for b in range(1, nb + 1)]
+        spans = []
+        for name, g, b in want:
+            rc, off, nbytes, eb = slot(eng, name, g, b)
+            assert rc == 0, (name, g, b)
+            assert eb == (4 if name == "PACC" else esz)
+            assert nbytes == (N * nstrips * 128 * 4 if name == "PACC" else N * h * w * 64 * esz)
+            assert off % 256 == 0 and off + nbytes <= total.value, (name, g, b)
+            spans.append((off, off + nbytes, (name, g, b)))
+        spans.sort()
+        for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
+            assert a1 <= b0, (ka, kb)
+        for name, g, b in (("GRB", 0, 1), ("GRB", nl, 0), ("STREAM", 0, nb + 1), ("STREAM", -1, 0), ("PACC", 0, 0),
+                           ("DZ", 0, nb + 1), ("DU", 0, 0)):
+            assert slot(eng, name, g, b)[0] == -10001, (name, g, b)
+        off, n, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        assert lib.srmi_engine_trace_slot(eng, 9, 0, 0, C.byref(off), C.byref(n), C.byref(eb)) == -10001
+        raw = (C.c_char * (total.value + 512))()
+        base = (C.addressof(raw) + 255) & ~255
+        assert lib.srmi_engine_trace(eng, C.c_void_p(base), total.value) == 0
+        assert lib.srmi_engine_trace(eng, C.c_void_p(base), total.value - 1) == -10003
+        assert lib.srmi_engine_trace(eng, C.c_void_p(base + 2), total.value) == -10003
+        assert lib.srmi_engine_trace(eng, None, 0) == 0
+        assert lib.srmi_engine_trace(None, None, 0) == -10001
+        lib.srmi_engine_destroy(eng)
+        inf, ws = make(spec, 0)
+        assert lib.srmi_engine_trace_size(inf, C.byref(total)) == -10001
+        assert lib.srmi_engine_trace(inf, None, 0) == -10001
+        lib.srmi_engine_destroy(inf)
+    edsr, ws = make(NetSpec(arch="edsr", nchannels_in=1, nchannels_out=1, nlayers=nl, scale=4, dtype="fp32"), 1)
+    assert lib.srmi_engine_trace_size(edsr, C.byref(total)) == -10001
+    lib.srmi_engine_destroy(edsr)
+
+
 @pytest.mark.parametrize("C", [1, 2])
 def test_native_param_plan_matches_reference_state_dict(C):
     from srmi.engine import NetSpec, param_table
