@@ -161,7 +161,9 @@ int srmi_backward_stages(srmi_engine* e, const float* params, const float* lr, c
  * forward's n -- the partial slabs of such a launch are one per (image, row chunk,
  * 48-column block); which = 7 (nothing launched): bit 0 the RCAB backward's dgrad and
  * filter gradient run as one fused launch, bit 1 the RCAB filter gradients' partial
- * slabs are bf16, bit 2 = which 4. */
+ * slabs are bf16, bit 2 = which 4; which = 8 (nothing launched, any RCAN engine): how the
+ * forward runs an RCAB -- 0 three launches (conv1, conv2 + pool writing u, the CA pass), 1 the
+ * training form with the CA inside conv2's launch, 2 the one-launch inference RCAB. */
 int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
 
 /* diagnostic (tests): device address, element count and element size of one of the
@@ -185,6 +187,11 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
 #define SRMI_BUF_DZ 7
 #define SRMI_BUF_DRESF 8
 #define SRMI_BUF_GROUP_IN_GRAD 9
+/* RESB: the body tail's output in the operand type (the upsamplers' input); PS(g = k): upsampler
+ * k's pixel-shuffled output [batch][lr_h 2^(k+1)][lr_w 2^(k+1)][64], k = 0 .. log2(scale) - 1.
+ * Both persist after a forward, in inference engines too. */
+#define SRMI_BUF_RESB 10
+#define SRMI_BUF_PS 11
 int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size_t* elems, int* elem_bytes);
 
 /* diagnostic (tests): trace of the RCAN backward's in-group state, which every RCAB of a
@@ -213,6 +220,34 @@ int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size
 int srmi_engine_trace_size(srmi_engine* e, size_t* bytes);
 int srmi_engine_trace(srmi_engine* e, void* buf, size_t bytes);
 int srmi_engine_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offset, size_t* elems, int* elem_bytes);
+
+/* diagnostic (tests): trace of the bf16 RCAN forward's transient state, under the backward
+ * trace's contract (the caller's 256-byte aligned buffer of at least srmi_engine_fwd_trace_size
+ * bytes, NULL = off, the default; asynchronous device-to-device copies on the forward's stream,
+ * between its launches; no launch, operand or order changes; one host branch per copy site when
+ * off).  Slots (which, g, b), g = residual group, b = RCAB 1 .. nblocks:
+ *   LO    the pair's lo8 remainder bytes [batch][lr_h][lr_w][64] after RCAB b (every RCAB
+ *         rewrites them in place);
+ *   PPOOL fp32 [batch][nstrips][64], the CA strip records after the launch that writes them:
+ *         conv1 where the CA runs inside conv2 and in the one-launch inference RCAB (sums of
+ *         the bf16 t), conv2 in the CA-pass forms (sums of its fp32 output);
+ *   RF    (b = 0) the fp32 output of group g after its tail conv;
+ * and, inference engines only (their hb / t / record slots rotate):
+ *   HB    (b = 0 .. nblocks; and g = nlayers, b = 0) as SRMI_BUF_HB of a train engine;
+ *   T     conv1's output of RCAB b;
+ *   REC   fp32 [batch][160], the CA record m | z1 | s of RCAB b.
+ * The first n images' share of each is copied.  bf16 RCAN engines, train or inference (the
+ * exact-fp32 engine and EDSR: SRMI_ERR_ARG).  srmi.inference and the trainers never set it. */
+#define SRMI_FTRACE_LO 0
+#define SRMI_FTRACE_PPOOL 1
+#define SRMI_FTRACE_RF 2
+#define SRMI_FTRACE_HB 3
+#define SRMI_FTRACE_T 4
+#define SRMI_FTRACE_REC 5
+int srmi_engine_fwd_trace_size(srmi_engine* e, size_t* bytes);
+int srmi_engine_fwd_trace(srmi_engine* e, void* buf, size_t bytes);
+int srmi_engine_fwd_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offset, size_t* elems,
+                               int* elem_bytes);
 
 /* RMSE (l2loss, squared=False).  loss4[0] = sum of squares (this rank),
  * loss4[1] = global element count; after the optional all-reduce of loss4[0],

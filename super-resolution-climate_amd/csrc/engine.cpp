@@ -239,6 +239,8 @@ struct srmi_engine {
   // diagnostic (srmi_engine_trace): the caller's buffer the RCAN backward copies its in-group
   // state into, one region per residual group; null = off (one branch per copy site)
   char* trace = nullptr;
+  // diagnostic (srmi_engine_fwd_trace): the same for the bf16 RCAN forward's transient state
+  char* ftrace = nullptr;
 
   bf16_t* at(bf16_t* base, size_t elems) const {
     return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(base) + elems * esz);
@@ -600,6 +602,87 @@ static int trace_copy(const srmi_engine* e, int which, int g, int b, const void*
   return err == hipSuccess ? 0 : -(int)err;
 }
 
+// ---- the forward trace (srmi_engine_fwd_trace): layout of the caller's buffer.  Per residual
+// group g, 256-byte aligned pieces in this order: LO b = 1 .. nb | PPOOL b = 1 .. nb | RF, and for
+// inference engines (whose hb / t / record slots rotate) HB b = 0 .. nb | T b = 1 .. nb | REC b =
+// 1 .. nb; after the last group an inference engine's HB(nlayers, 0).  LO is [N][h][w][64] bytes,
+// PPOOL fp32 [N][nstrips][64], RF an fp32 map, HB / T bf16 maps, REC fp32 [N][160] (capacity N:
+// the first n images' share is copied).
+static size_t ftrace_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t ftrace_piece_bytes(const srmi_engine* e, int which, int n) {
+  const size_t px = (size_t)n * e->h * e->w * 64;
+  switch (which) {
+    case SRMI_FTRACE_LO: return px;
+    case SRMI_FTRACE_PPOOL: return (size_t)n * conv3x3_nstrips(e->h, e->w) * 64 * sizeof(float);
+    case SRMI_FTRACE_RF: return px * sizeof(float);
+    case SRMI_FTRACE_REC: return (size_t)n * 160 * sizeof(float);
+    default: return px * 2;  // HB, T
+  }
+}
+static size_t ftrace_slot_bytes(const srmi_engine* e, int which) {
+  return ftrace_align(ftrace_piece_bytes(e, which, e->N));
+}
+static size_t ftrace_group_bytes(const srmi_engine* e) {
+  const size_t nb = (size_t)e->P.cfg.nblocks;
+  size_t b = (ftrace_slot_bytes(e, SRMI_FTRACE_LO) + ftrace_slot_bytes(e, SRMI_FTRACE_PPOOL)) * nb +
+             ftrace_slot_bytes(e, SRMI_FTRACE_RF);
+  if (!e->train)
+    b += ftrace_slot_bytes(e, SRMI_FTRACE_HB) * (nb + 1) +
+         (ftrace_slot_bytes(e, SRMI_FTRACE_T) + ftrace_slot_bytes(e, SRMI_FTRACE_REC)) * nb;
+  return b;
+}
+static size_t ftrace_bytes(const srmi_engine* e) {
+  return ftrace_group_bytes(e) * (size_t)e->P.cfg.nlayers + (e->train ? 0 : ftrace_slot_bytes(e, SRMI_FTRACE_HB));
+}
+// the bf16 RCAN engines have this state (the exact-fp32 engine keeps no pair, EDSR no CA)
+static bool ftrace_engine(const srmi_engine* e) { return e && !e->f32 && e->P.cfg.arch == SRMI_ARCH_RCAN; }
+// byte offset of slot (which, g, b), or (size_t)-1 if there is no such slot
+static size_t ftrace_offset(const srmi_engine* e, int which, int g, int b) {
+  const int nl = e->P.cfg.nlayers, nb = e->P.cfg.nblocks;
+  if (!e->train && which == SRMI_FTRACE_HB && g == nl && b == 0) return ftrace_group_bytes(e) * (size_t)nl;
+  if (g < 0 || g >= nl) return (size_t)-1;
+  const size_t lo = ftrace_slot_bytes(e, SRMI_FTRACE_LO), pp = ftrace_slot_bytes(e, SRMI_FTRACE_PPOOL),
+               rf = ftrace_slot_bytes(e, SRMI_FTRACE_RF), hbb = ftrace_slot_bytes(e, SRMI_FTRACE_HB),
+               tb = ftrace_slot_bytes(e, SRMI_FTRACE_T), rc = ftrace_slot_bytes(e, SRMI_FTRACE_REC);
+  const size_t base = ftrace_group_bytes(e) * (size_t)g, inf = base + (lo + pp) * (size_t)nb + rf;
+  const bool b1 = b >= 1 && b <= nb;
+  switch (which) {
+    case SRMI_FTRACE_LO:
+      return b1 ? base + lo * (size_t)(b - 1) : (size_t)-1;
+    case SRMI_FTRACE_PPOOL:
+      return b1 ? base + lo * (size_t)nb + pp * (size_t)(b - 1) : (size_t)-1;
+    case SRMI_FTRACE_RF:
+      return b == 0 ? base + (lo + pp) * (size_t)nb : (size_t)-1;
+    case SRMI_FTRACE_HB:
+      return !e->train && b >= 0 && b <= nb ? inf + hbb * (size_t)b : (size_t)-1;
+    case SRMI_FTRACE_T:
+      return !e->train && b1 ? inf + hbb * (size_t)(nb + 1) + tb * (size_t)(b - 1) : (size_t)-1;
+    case SRMI_FTRACE_REC:
+      return !e->train && b1 ? inf + hbb * (size_t)(nb + 1) + tb * (size_t)nb + rc * (size_t)(b - 1) : (size_t)-1;
+    default:
+      return (size_t)-1;
+  }
+}
+// one async device-to-device copy of the first n images' share of src into the slot
+static int ftrace_copy(const srmi_engine* e, int which, int g, int b, const void* src, int n, hipStream_t st) {
+  const size_t off = ftrace_offset(e, which, g, b);
+  if (off == (size_t)-1) return SRMI_ERR_ARG;
+  const hipError_t err =
+      hipMemcpyAsync(e->ftrace + off, src, ftrace_piece_bytes(e, which, n), hipMemcpyDeviceToDevice, st);
+  return err == hipSuccess ? 0 : -(int)err;
+}
+// the copies behind RCAB (g, b)'s last launch: the pair's lo8 bytes, and what an inference
+// engine's rotating slots hold of this RCAB (pool: the strip records too, where that launch or
+// the one before it wrote them and no launch between has its own copy site)
+static int ftrace_rcab(const srmi_engine* e, int g, int b, bool pool, int n, hipStream_t st) {
+  int rc = ftrace_copy(e, SRMI_FTRACE_LO, g, b, e->Hf, n, st);
+  if (!rc && pool) rc = ftrace_copy(e, SRMI_FTRACE_PPOOL, g, b, e->ppool, n, st);
+  if (!rc && !e->train) rc = ftrace_copy(e, SRMI_FTRACE_HB, g, b, e->hb(g, b), n, st);
+  if (!rc && !e->train) rc = ftrace_copy(e, SRMI_FTRACE_T, g, b, e->Tm(g, b), n, st);
+  if (!rc && !e->train) rc = ftrace_copy(e, SRMI_FTRACE_REC, g, b, e->recp(g, b), n, st);
+  return rc;
+}
+
 // SRMI_TRACE_ERRORS=1 in the environment: every failing step prints its line
 static int trace_rc(int rc, int line) {
   static const bool on = std::getenv("SRMI_TRACE_ERRORS") != nullptr;
@@ -666,6 +749,7 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
   const int h = e->h, w = e->w, HW = h * w;
   const int nstrips = conv3x3_nstrips(h, w);
   RC(head_fwd_launch(lr, prm + P.head.w, prm + P.head.b, n, e->C, h, w, e->X0f, e->hb(0, 0), e->f32, st));
+  if (e->ftrace && !e->train) RC(ftrace_copy(e, SRMI_FTRACE_HB, 0, 0, e->hb(0, 0), n, st));
   if (P.cfg.arch == SRMI_ARCH_RCAN) {
     const int nl = P.cfg.nlayers, nb = P.cfg.nblocks, R = P.cfg.reduction;
     for (int g = 0; g < nl; ++g) {
@@ -679,6 +763,7 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
           RC(rcab_infer_launch(c1, c2, e->ppool, nstrips, prm + r.ca_w1, prm + r.ca_b1, prm + r.ca_w2, prm + r.ca_b2,
                                64 / R, b == 1 ? rin : nullptr, b == 1 ? nullptr : e->hb(g, b - 1),
                                b == 1 ? nullptr : lo, e->hb(g, b), lo, e->recp(g, b), st));
+          if (e->ftrace) RC(ftrace_rcab(e, g, b, true, n, st));
           continue;
         }
         if (ca_fwd_mode(e)) {  // training: the CA forward inside conv2
@@ -696,6 +781,7 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
             c1.cas_on = 1;
           }
           RC(conv3x3_launch(c1, EPI_RELU_POOL, st));
+          if (e->ftrace) RC(ftrace_copy(e, SRMI_FTRACE_PPOOL, g, b, e->ppool, n, st));
           c2.r1h = b == 1 ? nullptr : e->hb(g, b - 1);
           c2.r1l = b == 1 ? nullptr : lo;
           c2.yph = e->hb(g, b);
@@ -709,6 +795,7 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
           }
           c2.cas_on = 1;
           RC(conv3x3_launch(c2, EPI_CA_RESID_U, st));
+          if (e->ftrace) RC(ftrace_rcab(e, g, b, false, n, st));
           continue;
         }
         RC(conv_fwd(e, r.c1, e->hb(g, b - 1), n, h, w, EPI_RELU_BF16, e->Tm(g, b), nullptr, nullptr, nullptr, 1.f, st));
@@ -724,10 +811,15 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
           RC(ca_fwd_launch(e->Um(g, b), e->ppool, nstrips, prm + r.ca_w1, prm + r.ca_b1, prm + r.ca_w2, prm + r.ca_b2,
                            n, HW, 64, R, b == 1 ? rin : nullptr, nullptr, e->hb(g, b), e->recp(g, b), 0, st,
                            b == 1 ? nullptr : e->hb(g, b - 1), b == 1 ? nullptr : lo, lo));
+          if (e->ftrace) RC(ftrace_rcab(e, g, b, true, n, st));
         }
       }
       RC(conv_fwd(e, P.group_tail[g], e->hb(g, nb), n, h, w, EPI_RESID, e->hb(g + 1, 0), e->Rf, rin, nullptr, 1.f,
                   st));
+      if (e->ftrace) {
+        RC(ftrace_copy(e, SRMI_FTRACE_RF, g, 0, e->Rf, n, st));
+        if (!e->train) RC(ftrace_copy(e, SRMI_FTRACE_HB, g + 1, 0, e->hb(g + 1, 0), n, st));
+      }
     }
     RC(conv_fwd(e, P.body_tail, e->hb(nl, 0), n, h, w, EPI_RESID, e->RESb, nullptr, e->X0f, nullptr, 1.f, st));
   } else {
@@ -1094,6 +1186,10 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
                            e->recp(0, 2), S_(stream)));
     return 0;
   }
+  if (which == 8) {  // how the forward runs an RCAB
+    if (!e || e->P.cfg.arch != SRMI_ARCH_RCAN) return SRMI_ERR_ARG;
+    return use_rcab_infer(e) ? 2 : ca_fwd_mode(e) ? 1 : 0;
+  }
   if (which == 5 || which == 6) {  // the filter gradients' row chunks per image of F1 (5) / F2 (6)
     if (!e || !e->train || e->P.cfg.arch != SRMI_ARCH_RCAN || e->last_n < 1) return SRMI_ERR_ARG;
     return rcab_row_splits(e, e->last_n, which == 5 ? 1 : 2);
@@ -1203,6 +1299,14 @@ int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size
       p = ((nl - 1 - g) & 1) ? e->GAf : e->GBf;
       eb = 4;
       break;
+    case SRMI_BUF_RESB:  // (both persist after a forward, in inference engines too)
+      p = e->RESb;
+      break;
+    case SRMI_BUF_PS:
+      if (g < 0 || g >= e->P.nups) return SRMI_ERR_ARG;
+      p = e->PS[g];
+      n = e->mapn << (2 * (g + 1));
+      break;
     default:
       return SRMI_ERR_ARG;
   }
@@ -1234,6 +1338,31 @@ int srmi_engine_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offs
   *offset = off;
   *elems = which == SRMI_TRACE_PACC ? (size_t)e->N * conv3x3_nstrips(e->h, e->w) * 128 : e->mapn;
   *elem_bytes = which == SRMI_TRACE_PACC ? 4 : (int)e->esz;
+  return 0;
+}
+
+int srmi_engine_fwd_trace_size(srmi_engine* e, size_t* bytes) {
+  if (!ftrace_engine(e) || !bytes) return SRMI_ERR_ARG;
+  *bytes = ftrace_bytes(e);
+  return 0;
+}
+
+int srmi_engine_fwd_trace(srmi_engine* e, void* buf, size_t bytes) {
+  if (!ftrace_engine(e)) return SRMI_ERR_ARG;
+  if (buf && (bytes < ftrace_bytes(e) || ((uintptr_t)buf & 255))) return SRMI_ERR_WORKSPACE;
+  e->ftrace = static_cast<char*>(buf);
+  return 0;
+}
+
+int srmi_engine_fwd_trace_slot(srmi_engine* e, int which, int g, int b, size_t* offset, size_t* elems,
+                               int* elem_bytes) {
+  if (!ftrace_engine(e) || !offset || !elems || !elem_bytes) return SRMI_ERR_ARG;
+  const size_t off = ftrace_offset(e, which, g, b);
+  if (off == (size_t)-1) return SRMI_ERR_ARG;
+  const int eb = which == SRMI_FTRACE_LO ? 1 : (which == SRMI_FTRACE_HB || which == SRMI_FTRACE_T) ? 2 : 4;
+  *offset = off;
+  *elems = ftrace_piece_bytes(e, which, e->N) / (size_t)eb;
+  *elem_bytes = eb;
   return 0;
 }
 

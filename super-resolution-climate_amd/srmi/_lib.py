@@ -26,9 +26,12 @@ SRMI_LOSS_MEAN = 1
 SRMI_INTERP_BILINEAR = 1
 SRMI_INTERP_BICUBIC = 2
 # srmi_engine_buffer's `which` (SRMI_BUF_*)
-BUFFERS = {"X0F": 0, "HB": 1, "T": 2, "U": 3, "REC": 4, "BREC": 5, "DU": 6, "DZ": 7, "DRESF": 8, "GROUP_IN_GRAD": 9}
+BUFFERS = {"X0F": 0, "HB": 1, "T": 2, "U": 3, "REC": 4, "BREC": 5, "DU": 6, "DZ": 7, "DRESF": 8, "GROUP_IN_GRAD": 9,
+           "RESB": 10, "PS": 11}
 # srmi_engine_trace_slot's `which` (SRMI_TRACE_*)
 TRACE_SLOTS = {"GRB": 0, "STREAM": 1, "PACC": 2, "DZ": 3, "DU": 4}
+# srmi_engine_fwd_trace_slot's `which` (SRMI_FTRACE_*)
+FWD_TRACE_SLOTS = {"LO": 0, "PPOOL": 1, "RF": 2, "HB": 3, "T": 4, "REC": 5}
 TILE_LOSS_SUB = 16  # parts per tile of srmi_tile_loss_parts
 
 ERRORS = {-10001: "SRMI_ERR_ARG", -10002: "SRMI_ERR_SHAPE", -10003: "SRMI_ERR_WORKSPACE",
@@ -67,6 +70,10 @@ _SIGS = {
     "srmi_engine_trace": ([P, P, C.c_size_t], C.c_int),
     "srmi_engine_trace_slot": ([P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int)], C.c_int),
+    "srmi_engine_fwd_trace_size": ([P, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_engine_fwd_trace": ([P, P, C.c_size_t], C.c_int),
+    "srmi_engine_fwd_trace_slot": ([P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_int)], C.c_int),
     "srmi_rmse_partial": ([P, P, P, C.c_size_t, C.c_double, P, P], C.c_int),
     "srmi_rmse_finalize": ([P, P], C.c_int),
     "srmi_charbonnier_partial": ([P, P, P, C.c_size_t, C.c_double, C.c_float, P, P, P], C.c_int),

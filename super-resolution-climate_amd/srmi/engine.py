@@ -148,7 +148,8 @@ class Engine:
         """Diagnostic (tests): one of the engine's saved maps as a view into the workspace
         (no copy; srmi_engine_buffer), valid until the next forward / backward.  name:
         a key of _lib.BUFFERS.  Maps come as [n, h, w, 64] (n = the last forward's tiles)
-        in the map's own type, the CA records REC / BREC as [n, 160] / [n, 224] fp32."""
+        in the map's own type, the CA records REC / BREC as [n, 160] / [n, 224] fp32, the
+        upsamplers' outputs PS (g = k) as [n, h 2^(k+1), w 2^(k+1), 64]."""
         if name not in _lib.BUFFERS:
             raise _lib.SrmiError(f"unknown engine buffer {name!r} ({' | '.join(_lib.BUFFERS)})")
         p, elems, eb = C.c_void_p(), C.c_size_t(), C.c_int()
@@ -161,6 +162,8 @@ class Engine:
         flat = self.workspace[off:off + nbytes].view(torch.float32 if eb.value == 4 else torch.bfloat16)
         n = getattr(self, "_last_n", self.batch)
         per = int(elems.value) // self.batch
+        if name == "PS":
+            return flat.view(self.batch, self.lr_h << (g + 1), self.lr_w << (g + 1), 64)[:n]
         return flat.view(self.batch, *((self.lr_h, self.lr_w, 64) if name not in ("REC", "BREC") else (per,)))[:n]
 
     def trace(self, on: bool = True) -> Optional[torch.Tensor]:
@@ -198,9 +201,48 @@ class Engine:
         shape = (self.lr_h, self.lr_w, 64) if name != "PACC" else (int(elems.value) // self.batch // 128, 128)
         return flat.view(self.batch, *shape)[:n]
 
+    def fwd_trace(self, on: bool = True) -> Optional[torch.Tensor]:
+        """Diagnostic (tests): turn the forward trace on (a buffer of srmi_engine_fwd_trace_size
+        bytes, owned by this object and returned) or off (srmi_engine_fwd_trace).  While on, every
+        forward copies the state its launches rewrite in place into the buffer (async copies on
+        the forward's stream); fwd_trace_view reads a slot.  bf16 RCAN engines."""
+        if not on:
+            call("srmi_engine_fwd_trace", self._h, None, 0)
+            self._fwd_trace = None
+            return None
+        nbytes = C.c_size_t()
+        call("srmi_engine_fwd_trace_size", self._h, C.byref(nbytes))
+        buf = torch.zeros(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        call("srmi_engine_fwd_trace", self._h, ptr(buf), buf.numel())
+        self._fwd_trace = buf
+        return buf
+
+    def fwd_trace_view(self, name: str, g: int = 0, b: int = 0) -> torch.Tensor:
+        """One slot of the forward trace buffer as a view (no copy): LO [n, h, w, 64] uint8,
+        PPOOL [n, nstrips, 64] fp32, RF [n, h, w, 64] fp32, and of inference engines HB / T
+        [n, h, w, 64] bf16 and REC [n, 160] fp32.  name: a key of _lib.FWD_TRACE_SLOTS."""
+        if getattr(self, "_fwd_trace", None) is None:
+            raise _lib.SrmiError("the forward trace is off (Engine.fwd_trace())")
+        if name not in _lib.FWD_TRACE_SLOTS:
+            raise _lib.SrmiError(f"unknown forward trace slot {name!r} ({' | '.join(_lib.FWD_TRACE_SLOTS)})")
+        off, elems, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        call("srmi_engine_fwd_trace_slot", self._h, _lib.FWD_TRACE_SLOTS[name], int(g), int(b), C.byref(off),
+             C.byref(elems), C.byref(eb))
+        nbytes = int(elems.value) * eb.value
+        if off.value + nbytes > self._fwd_trace.numel():
+            raise _lib.SrmiError(f"forward trace slot {name} lies outside the trace buffer")
+        flat = self._fwd_trace[off.value:off.value + nbytes]
+        if eb.value != 1:
+            flat = flat.view(torch.float32 if eb.value == 4 else torch.bfloat16)
+        n = getattr(self, "_last_n", self.batch)
+        per = int(elems.value) // self.batch
+        shape = {"PPOOL": (per // 64, 64), "REC": (per,)}.get(name, (self.lr_h, self.lr_w, 64))
+        return flat.view(self.batch, *shape)[:n]
+
     def probe(self, which: int, reps: int = 1, stream=None) -> int:
         """srmi_engine_probe: which = 4 du formed inside F2; 5 / 6 the filter gradients' row
-        chunks per image in F1 / F2; 7 bit 0 fused launches, bit 1 bf16 partial slabs, bit 2 = 4."""
+        chunks per image in F1 / F2; 7 bit 0 fused launches, bit 1 bf16 partial slabs, bit 2 = 4;
+        8 the forward's RCAB form: 0 the CA pass, 1 the CA inside conv2, 2 the one-launch RCAB."""
         return call("srmi_engine_probe", self._h, int(which), int(reps), stream_handle(stream))
 
     def rmse_partial(self, pred: torch.Tensor, target: torch.Tensor, loss4: torch.Tensor, count_global: float,

@@ -156,6 +156,112 @@ def test_trace_slots_tile_the_trace_buffer_without_overlap():
     lib.srmi_engine_destroy(edsr)
 
 
+def test_forward_trace_slots_and_new_buffers():
+    """srmi_engine_fwd_trace_size / _fwd_trace / _fwd_trace_slot and SRMI_BUF_RESB / _PS on
+    engines carved over host buffers (nothing is launched): every slot is 256-byte aligned, of
+    its documented size, inside the reported size and disjoint from the others; an inference
+    engine has the HB / T / REC slots a train engine refuses; a short or misaligned buffer, the
+    exact-fp32 engine and EDSR are refused, NULL turns it off; RESB and PS(k) lie in the
+    workspace beside the other maps, in inference engines too."""
+    import ctypes as C
+    from srmi import _lib
+    from srmi.engine import NetSpec
+    lib = _lib.load()
+    nl, nb, N, h, w = 2, 3, 3, 8, 48
+
+    def make(spec, train):
+        cfg = spec.cstruct(N, h, w)
+        nbytes = C.c_size_t()
+        assert lib.srmi_workspace_size(C.byref(cfg), train, C.byref(nbytes)) == 0
+        ws = (C.c_char * (nbytes.value + 256))()
+        eng = C.c_void_p()
+        assert lib.srmi_engine_create(C.byref(cfg), ws, len(ws), train, C.byref(eng)) == 0
+        return eng, ws
+
+    def slot(eng, name, g, b):
+        off, n, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        rc = lib.srmi_engine_fwd_trace_slot(eng, _lib.FWD_TRACE_SLOTS[name], g, b, C.byref(off), C.byref(n),
+                                            C.byref(eb))
+        return rc, off.value, n.value * eb.value, eb.value
+
+    def buf(eng, name, g=0, b=0):
+        p, n, eb = C.c_void_p(), C.c_size_t(), C.c_int()
+        rc = lib.srmi_engine_buffer(eng, _lib.BUFFERS[name], g, b, C.byref(p), C.byref(n), C.byref(eb))
+        return rc, p.value, n.value * eb.value, eb.value
+
+    for name in ("srmi_engine_fwd_trace_size", "srmi_engine_fwd_trace", "srmi_engine_fwd_trace_slot"):
+        assert hasattr(lib, name) and name in _lib.EXPORTED
+    assert _lib.BUFFERS["GROUP_IN_GRAD"] == 9 and _lib.BUFFERS["RESB"] == 10 and _lib.BUFFERS["PS"] == 11
+    assert _lib.TRACE_SLOTS == {"GRB": 0, "STREAM": 1, "PACC": 2, "DZ": 3, "DU": 4}
+    nstrips = lib.srmi_conv3x3_nstrips(h, w)
+    px = N * h * w * 64
+    size = {"LO": (px, 1), "PPOOL": (N * nstrips * 64 * 4, 4), "RF": (px * 4, 4), "HB": (px * 2, 2), "T": (px * 2, 2),
+            "REC": (N * 160 * 4, 4)}
+    spec = NetSpec(arch="rcan", nchannels_in=1, nchannels_out=1, nlayers=nl, nblocks=nb, scale=4, dtype="bf16")
+    common = [(k, g, b) for k in ("LO", "PPOOL") for g in range(nl) for b in range(1, nb + 1)]
+    common += [("RF", g, 0) for g in range(nl)]
+    infer_only = [("HB", g, b) for g in range(nl) for b in range(nb + 1)] + [("HB", nl, 0)]
+    infer_only += [(k, g, b) for k in ("T", "REC") for g in range(nl) for b in range(1, nb + 1)]
+    totals = {}
+    for train in (1, 0):
+        eng, ws = make(spec, train)
+        total = C.c_size_t()
+        assert lib.srmi_engine_fwd_trace_size(eng, C.byref(total)) == 0
+        totals[train] = total.value
+        spans = []
+        for name, g, b in common + ([] if train else infer_only):
+            rc, off, nbytes, eb = slot(eng, name, g, b)
+            assert rc == 0, (name, g, b)
+            assert (nbytes, eb) == size[name], (name, g, b)
+            assert off % 256 == 0 and off + nbytes <= total.value, (name, g, b)
+            spans.append((off, off + nbytes, (name, g, b)))
+        spans.sort()
+        for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
+            assert a1 <= b0, (ka, kb)
+        bad = [("LO", 0, 0), ("LO", 0, nb + 1), ("LO", nl, 1), ("LO", -1, 1), ("PPOOL", 0, 0), ("RF", 0, 1),
+               ("RF", nl, 0), ("HB", nl, 1), ("HB", nl + 1, 0), ("HB", 0, nb + 1), ("T", 0, 0), ("REC", 0, nb + 1)]
+        for name, g, b in bad + (infer_only if train else []):
+            assert slot(eng, name, g, b)[0] == -10001, (train, name, g, b)
+        off, n, eb = C.c_size_t(), C.c_size_t(), C.c_int()
+        assert lib.srmi_engine_fwd_trace_slot(eng, 9, 0, 1, C.byref(off), C.byref(n), C.byref(eb)) == -10001
+        assert lib.srmi_engine_fwd_trace_slot(eng, 0, 0, 1, None, C.byref(n), C.byref(eb)) == -10001
+        raw = (C.c_char * (total.value + 512))()
+        base = (C.addressof(raw) + 255) & ~255
+        assert lib.srmi_engine_fwd_trace(eng, C.c_void_p(base), total.value) == 0
+        assert lib.srmi_engine_fwd_trace(eng, C.c_void_p(base), total.value - 1) == -10003
+        assert lib.srmi_engine_fwd_trace(eng, C.c_void_p(base + 2), total.value) == -10003
+        assert lib.srmi_engine_fwd_trace(eng, None, 0) == 0
+        assert lib.srmi_engine_fwd_trace_size(eng, None) == -10001
+        # RESB and PS(k): in the workspace, disjoint from each other and from the other maps
+        wbase = C.addressof(ws)
+        maps = [("X0F", 0, 0, px * 4), ("RESB", 0, 0, px * 2), ("PS", 0, 0, px * 4 * 2), ("PS", 1, 0, px * 16 * 2)]
+        if train:
+            maps += [("HB", nl, 0, px * 2), ("T", nl - 1, nb, px * 2), ("U", nl - 1, nb, px * 2)]
+        spans = []
+        for name, g, b, want in maps:
+            rc, p, nbytes, eb = buf(eng, name, g, b)
+            assert rc == 0 and nbytes == want, (name, g)
+            assert wbase <= p and p + nbytes <= wbase + len(ws), (name, g)
+            spans.append((p, p + nbytes, (name, g)))
+        spans.sort()
+        for (a0, a1, ka), (b0, b1, kb) in zip(spans, spans[1:]):
+            assert a1 <= b0, (ka, kb)
+        assert buf(eng, "PS", 2)[0] == -10001 and buf(eng, "PS", -1)[0] == -10001
+        assert lib.srmi_engine_probe(eng, 8, 1, None) == (1 if train else 2)
+        lib.srmi_engine_destroy(eng)
+    assert totals[0] > totals[1]
+    assert lib.srmi_engine_fwd_trace_size(None, C.byref(total)) == -10001
+    assert lib.srmi_engine_fwd_trace(None, None, 0) == -10001
+    for other in (NetSpec(arch="rcan", nchannels_in=1, nchannels_out=1, nlayers=nl, nblocks=nb, scale=4, dtype="fp32"),
+                  NetSpec(arch="edsr", nchannels_in=1, nchannels_out=1, nlayers=nl, scale=4, dtype="bf16")):
+        eng, ws = make(other, 1)
+        assert lib.srmi_engine_fwd_trace_size(eng, C.byref(total)) == -10001
+        assert lib.srmi_engine_fwd_trace(eng, None, 0) == -10001
+        assert slot(eng, "LO", 0, 1)[0] == -10001
+        assert buf(eng, "RESB")[0] == 0 and buf(eng, "PS", 1)[0] == 0
+        lib.srmi_engine_destroy(eng)
+
+
 @pytest.mark.parametrize("C", [1, 2])
 def test_native_param_plan_matches_reference_state_dict(C):
     from srmi.engine import NetSpec, param_table
