@@ -30,6 +30,9 @@
  *                                   sres/base/source/swot/raw.py:216-233, :169-181
  *   srmi_batch_prep              -> norm 'lnorm' (swot/raw.py:169-181) + xyflip
  *                                   sres/base/source/batch.py:37-49 + downsample
+ *   srmi_*_norm                  -> every branch of norm, swot/raw.py:169-214
+ *   srmi_tile_stats*             -> _compute_normalization + globalize_norm
+ *                                   sres/base/source/swot/raw.py:89-106, :23-30
  *   srmi_llc_*, srmi_tiles_*     -> SWOTRawDataLoader.load_file + get_tiles
  *                                   sres/base/source/swot/raw.py:133-145, :216-233
  *   srmi_tiles_to_region         -> denorm + assemble_images
@@ -388,6 +391,52 @@ int srmi_tiles_to_region(const float* tiles, const float* mean, const float* std
  * skipped).  T even. */
 int srmi_batch_prep(const float* raw, int B, int C, int T, int flip_index, int scale, float* hr, float* lr,
                     float* mean, float* std, void* stream);
+
+/* ---- every task.norm mode, and the dataset tile statistics ------------- */
+/* norm() (sres/base/source/swot/raw.py:169-214) has six branches.  On the device
+ * they are three modes: the two that take their statistics from the tile itself,
+ * and one that is handed an offset and a divisor per (tile, channel) -- 'gnorm'
+ * (raw.py:187-191), 'gscale' (:192-195), 'tnorm' (:196-203) and 'tscale'
+ * (:204-209) differ only in which statistics the caller puts there
+ * (srmi.norm.NormStats.offsets). */
+#define SRMI_NORM_LNORM 0  /* (x - mean) / std of the tile          (raw.py:177-181) */
+#define SRMI_NORM_LSCALE 1 /* (x - min) / (max - min) of the tile   (raw.py:182-186) */
+#define SRMI_NORM_AFFINE 2 /* (x - off[b][c]) / div[b][c], caller's (raw.py:187-209) */
+
+/* srmi_batch_prep with a norm mode.  LNORM is srmi_batch_prep itself (off_out =
+ * mean, div_out = std; B <= 65535).  LSCALE: off_out [B][C] = min, div_out =
+ * max - min in fp32 (NULL: skipped); the tile is divided by the exact difference,
+ * so its extremes are exactly 0 and 1.  AFFINE: hr = fp32(((double)x - off) / div)
+ * to within one fp32 ulp (the quotient is a product with the fp64 reciprocal);
+ * off / div [B][C]; off_out / div_out are not written.  LSCALE and AFFINE take any
+ * B with B * C < 2^31 (a whole time slice); their raw and hr must be 16-byte
+ * aligned (SRMI_ERR_ARG otherwise).  div == 0 gives the IEEE result, as in the
+ * reference.  xyflip and the LR tile are srmi_batch_prep's. */
+int srmi_batch_prep_norm(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
+                         const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
+                         void* stream);
+/* srmi_region_to_tiles with a norm mode (get_tiles raw.py:216-233 + norm
+ * raw.py:169-214); off / div / off_out / div_out are [gy*gx][C], indexed by grid
+ * cell.  LNORM is srmi_region_to_tiles itself (off_out = mean, div_out = std, both
+ * required).  srmi_tiles_to_region (x * std + mean) undoes LSCALE with mean :=
+ * off_out, std := div_out, and AFFINE with off / div -- denorm's two branches
+ * (sres/controller/dual_trainer.py:67-77). */
+int srmi_region_to_tiles_norm(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
+                              const float* div, float* tiles, float* off_out, float* div_out, int* bad,
+                              void* stream);
+/* _compute_normalization (raw.py:89-106) for one time slice: tiles [n][C][ty][tx]
+ * (srmi_tiles_gather's result), acc [n][C][4] fp64 = {sum over calls of the
+ * plane's mean, sum of its variance (ddof 0), running max, running min} --
+ * NormData.add_entry (raw.py:55-60).  first != 0 initialises acc (max from -inf,
+ * min from +inf) instead of accumulating.  n * C < 2^31.  Deterministic. */
+int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream);
+/* tstats [n][C][4] = {sum mean / ntimes, sum var / ntimes, max, min}, the STATS
+ * order of NormData.get_norm_stats (raw.py:18, :62-63); gstats [C][4] =
+ * globalize_norm (raw.py:23-30): mean over the tiles of the means and of the
+ * variances, max of the max, min of the min, reduced in fp64 in a fixed order.
+ * Either output may be NULL; both must be 16-byte aligned. */
+int srmi_tile_stats_finalize(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
+                             void* stream);
 
 /* ---- on-disk LLC4320 source -> tiles --------------- */
 /* Replaces SWOTRawDataLoader.load_file (sres/base/source/swot/raw.py:133-145):

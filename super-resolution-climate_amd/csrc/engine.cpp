@@ -1577,6 +1577,29 @@ int srmi_batch_prep(const float* raw, int B, int C, int T, int flip_index, int s
   return batch_prep_launch(raw, B, C, T, flip_index, scale, hr, lr, mean, std, S_(stream));
 }
 
+int srmi_batch_prep_norm(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
+                         const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
+                         void* stream) {
+  return batch_prep_norm_launch(raw, B, C, T, flip_index, scale, mode, off, div, hr, lr, off_out, div_out,
+                                S_(stream));
+}
+
+int srmi_region_to_tiles_norm(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
+                              const float* div, float* tiles, float* off_out, float* div_out, int* bad,
+                              void* stream) {
+  return region_to_tiles_norm_launch(region, C, H, W, ty, tx, mode, off, div, tiles, off_out, div_out, bad,
+                                     S_(stream));
+}
+
+int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {
+  return tile_stats_launch(tiles, n, C, ty, tx, acc, first, S_(stream));
+}
+
+int srmi_tile_stats_finalize(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
+                             void* stream) {
+  return tile_stats_finalize_launch(acc, n, C, ntimes, tstats, gstats, S_(stream));
+}
+
 int srmi_region_to_tiles(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
                          float* std, int* bad, void* stream) {
   if (!region || !tiles || !mean || !std) return SRMI_ERR_ARG;

@@ -272,5 +272,15 @@ int tiles_gather_launch(const float* region, int C, int H, int W, int ty, int tx
                         float* out, hipStream_t st);
 int batch_prep_launch(const float* raw, int B, int C, int T, int flip, int scale, float* hr, float* lr, float* mean,
                       float* stdv, hipStream_t st);
+// the other task.norm modes and the dataset tile statistics (tiles.hip)
+int batch_prep_norm_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                           const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                           hipStream_t st);
+int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
+                                const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
+                                hipStream_t st);
+int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
+int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
+                               hipStream_t st);
 
 }  // namespace srmi

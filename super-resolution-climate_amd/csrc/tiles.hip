@@ -11,6 +11,10 @@
 // (sres/base/source/batch.py:37-49, applied by load_batch :301) and the
 // apply_network input downsample (array.py:72-76) -- one pass over HBM.
 //
+// batch_prep_norm / region_to_tiles_norm are the two above with the other five
+// branches of norm() (raw.py:182-209), and tile_stats the statistics pass they
+// need (_compute_normalization, raw.py:89-106, globalize_norm :23-30).
+//
 // llc_* replace SWOTRawDataLoader.load_file (swot/raw.py:133-145, mds2d
 // swot/util.py:3-7, subset_roi raw.py:38-45) and tiles_nonfinite/tiles_gather
 // the tiling of get_tiles (raw.py:216-233) -- SURVEY.md §8f row 3, see below.
@@ -339,6 +343,435 @@ int batch_prep_launch(const float* raw, int B, int C, int T, int flip, int scale
     hipLaunchKernelGGL(batch_prep_kernel<false>, dim3(C, B), dim3(kPrepThreads), 0, st, raw, C, T, flip, scale, hr,
                        lr, mean, stdv);
   }
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------- the other task.norm modes
+// norm() has six branches (raw.py:169-214).  'lnorm' is the kernels above.
+// 'lscale' is (x - min) / (max - min) of the tile; 'gnorm', 'gscale', 'tnorm' and
+// 'tscale' are all (x - off) / div with one offset and one divisor per (tile,
+// channel) taken from the dataset statistics (srmi.norm.NormStats.offsets): the
+// AFFINE mode.  x - off is formed in fp64 for the reason given above
+// batch_prep_kernel, the quotient as a product with the fp64 reciprocal (what that
+// kernel does with 1 / std; within one fp32 ulp of the division rounded once).
+// LSCALE divides by the exact fp64 max - min, so the tile's extremes come out as
+// exactly 0 and 1, as the reference's fp32 (max - min) / (max - min) does; the
+// divisor it reports is that difference rounded to fp32.
+template <int kThreads>
+__device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, o, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  }
+  constexpr int kW = kThreads / 64;
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[w] = mn;
+    red[kW + w] = mx;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kW; ++i) {
+    mn = fminf(mn, red[i]);
+    mx = fmaxf(mx, red[kW + i]);
+  }
+  __syncthreads();
+}
+
+// batch_prep_kernel with the plane (b * C + c) on grid.x -- a whole time slice is
+// one launch (srmi.norm.normalize_tiles) -- and the statistics of kMode.  The
+// flipped HR tile and the LR tile are written exactly as there.
+template <bool kLds, int kMode>
+__global__ void __launch_bounds__(kPrepThreads) batch_prep_norm_kernel(const float* __restrict__ raw, int T, int flip,
+                                                                       int scale, const float* __restrict__ off,
+                                                                       const float* __restrict__ dv,
+                                                                       float* __restrict__ hr, float* __restrict__ lr,
+                                                                       float* __restrict__ off_out,
+                                                                       float* __restrict__ div_out) {
+  extern __shared__ float tile[];  // [T][T + 1] when kLds
+  __shared__ float red[2 * kPrepThreads / 64];
+  const size_t p = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int n = T * T, P = kLds ? T + 1 : T;
+  const float* src = raw + p * n;
+  const float* buf = kLds ? tile : src;
+  float mn = INFINITY, mx = -INFINITY;
+  if (kLds || kMode == SRMI_NORM_LSCALE) {
+    for (int i = 4 * tid; i < n; i += 4 * kPrepThreads) {  // T even -> n % 4 == 0
+      const float4 v = *reinterpret_cast<const float4*>(src + i);
+      if (kMode == SRMI_NORM_LSCALE) {
+        mn = fminf(fminf(mn, v.x), fminf(v.y, fminf(v.z, v.w)));
+        mx = fmaxf(fmaxf(mx, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
+      }
+      if (kLds) {
+        const int y = i / T, x = i - y * T;
+        if (x + 3 < T) {
+          float* d = tile + y * P + x;
+          d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        } else {  // T % 4 == 2: the float4 straddles two rows
+          const float vv[4] = {v.x, v.y, v.z, v.w};
+          for (int e = 0; e < 4; ++e) {
+            const int ye = (i + e) / T, xe = (i + e) - ye * T;
+            tile[ye * P + xe] = vv[e];
+          }
+        }
+      }
+    }
+  }
+  double o, inv;
+  if (kMode == SRMI_NORM_LSCALE) {
+    block_minmax<kPrepThreads>(mn, mx, red);  // (also orders the LDS stores)
+    o = (double)mn;
+    inv = 1.0 / ((double)mx - (double)mn);
+  } else {
+    if (kLds) __syncthreads();
+    o = (double)off[p];
+    inv = 1.0 / (double)dv[p];
+  }
+  auto norm = [&](int y, int x) __attribute__((always_inline)) {
+    int sy, sx;
+    flip_src(flip, T, y, x, sy, sx);
+    return (float)(((double)buf[sy * P + sx] - o) * inv);
+  };
+  float* dst = hr + p * n;
+  for (int i = 4 * tid; i < n; i += 4 * kPrepThreads) {
+    float q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int y = (i + e) / T, x = (i + e) - y * T;
+      q[e] = norm(y, x);
+    }
+    *reinterpret_cast<float4*>(dst + i) = make_float4(q[0], q[1], q[2], q[3]);
+  }
+  if (lr) {
+    // downsample_kernel's arithmetic (small.hip), tap order as in batch_prep_kernel
+    const int t = T / scale;
+    const float k[4] = {-3.f / 32.f, 19.f / 32.f, 19.f / 32.f, -3.f / 32.f};
+    float* ldst = lr + p * t * t;
+    for (int i = tid; i < t * t; i += kPrepThreads) {
+      const int y = i / t, x = i - y * t;
+      const int y0 = y * scale + scale / 2 - 2, x0 = x * scale + scale / 2 - 2;
+      float acc = 0.f;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int yy = min(max(y0 + a, 0), T - 1);
+        float rsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rsum += k[j] * norm(yy, min(max(x0 + j, 0), T - 1));
+        acc += k[a] * rsum;
+      }
+      ldst[i] = acc;
+    }
+  }
+  if (kMode == SRMI_NORM_LSCALE && tid == 0) {
+    if (off_out) off_out[p] = mn;
+    if (div_out) div_out[p] = mx - mn;
+  }
+}
+
+int batch_prep_norm_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                           const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                           hipStream_t st) {
+  if (mode == SRMI_NORM_LNORM) {
+    if (B > 65535) return SRMI_ERR_SHAPE;  // batch_prep_launch's grid.y
+    return batch_prep_launch(raw, (int)B, C, T, flip, scale, hr, lr, off_out, div_out, st);
+  }
+  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
+  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
+  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
+  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
+#define SRMI_PREP_NORM(LDS, MODE, BYTES)                                                                          \
+  hipLaunchKernelGGL((batch_prep_norm_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
+                     lr, off_out, div_out)
+  if (lds <= 150 * 1024) {
+    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(true, SRMI_NORM_LSCALE, lds);
+    else SRMI_PREP_NORM(true, SRMI_NORM_AFFINE, lds);
+  } else {
+    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(false, SRMI_NORM_LSCALE, 0);
+    else SRMI_PREP_NORM(false, SRMI_NORM_AFFINE, 0);
+  }
+#undef SRMI_PREP_NORM
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// float4s a thread of the register-resident forms below holds: a 192^2 plane over 1024
+// threads (12, as region_to_tiles_reg_kernel, spills next to their fp64 arithmetic)
+constexpr int kNormKR = 9;
+
+// region_to_tiles_reg_kernel / region_to_tiles_kernel with the statistics of kMode;
+// off / dv are indexed by (grid cell, channel).  kVec: the tile in registers, float4.
+template <int kMode, bool kVec>
+__global__ void __launch_bounds__(1024) region_to_tiles_norm_kernel(const float* __restrict__ region, int C, int H,
+                                                                    int W, int ty, int tx, int gx,
+                                                                    const float* __restrict__ off,
+                                                                    const float* __restrict__ dv,
+                                                                    float* __restrict__ tiles,
+                                                                    float* __restrict__ off_out,
+                                                                    float* __restrict__ div_out,
+                                                                    int* __restrict__ bad) {
+  __shared__ float red[32];
+  const int c = blockIdx.x, t = blockIdx.y;
+  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
+  const int tx4 = tx >> 2, n4 = ty * tx4, n = ty * tx;
+  const size_t p = (size_t)t * C + c;
+  float4 v[kVec ? kNormKR : 1];
+  float mn = INFINITY, mx = -INFINITY;
+  int nonfinite = 0;
+  if (kVec) {
+#pragma unroll
+    for (int j = 0; j < kNormKR; ++j) {
+      const int i = threadIdx.x + j * 1024;
+      v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (i < n4) {
+        const int r = i / tx4, q = i - r * tx4;
+        v[j] = *reinterpret_cast<const float4*>(src + (size_t)r * W + 4 * q);
+        mn = fminf(fminf(mn, v[j].x), fminf(v[j].y, fminf(v[j].z, v[j].w)));
+        mx = fmaxf(fmaxf(mx, v[j].x), fmaxf(v[j].y, fmaxf(v[j].z, v[j].w)));
+        nonfinite |= !(isfinite(v[j].x) && isfinite(v[j].y) && isfinite(v[j].z) && isfinite(v[j].w));
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < n; i += 1024) {
+      const float a = src[(size_t)(i / tx) * W + (i % tx)];
+      mn = fminf(mn, a);
+      mx = fmaxf(mx, a);
+      nonfinite |= !isfinite(a);
+    }
+  }
+  double o, inv;
+  if (kMode == SRMI_NORM_LSCALE) {
+    block_minmax<1024>(mn, mx, red);
+    o = (double)mn;
+    inv = 1.0 / ((double)mx - (double)mn);
+  } else {
+    o = (double)off[p];
+    inv = 1.0 / (double)dv[p];
+  }
+  auto norm = [&](float a) __attribute__((always_inline)) { return (float)(((double)a - o) * inv); };
+  if (kVec) {
+    float4* dst = reinterpret_cast<float4*>(tiles + p * n);
+#pragma unroll
+    for (int j = 0; j < kNormKR; ++j) {
+      const int i = threadIdx.x + j * 1024;
+      if (i < n4) dst[i] = make_float4(norm(v[j].x), norm(v[j].y), norm(v[j].z), norm(v[j].w));
+    }
+  } else {
+    float* dst = tiles + p * n;
+    for (int i = threadIdx.x; i < n; i += 1024) dst[i] = norm(src[(size_t)(i / tx) * W + (i % tx)]);
+  }
+  const int anybad = __syncthreads_or(nonfinite);
+  if (threadIdx.x == 0) {
+    if (kMode == SRMI_NORM_LSCALE) {
+      if (off_out) off_out[p] = mn;
+      if (div_out) div_out[p] = mx - mn;
+    }
+    if (bad && anybad) atomicOr(&bad[t], 1);  // as region_to_tiles_kernel: the flag of a dropped tile
+  }
+}
+
+int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
+                                const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
+                                hipStream_t st) {
+  if (mode == SRMI_NORM_LNORM) {
+    if (!region || !tiles || !off_out || !div_out) return SRMI_ERR_ARG;
+    return region_to_tiles_launch(region, C, H, W, ty, tx, tiles, off_out, div_out, bad, st);
+  }
+  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  const int gy = H / ty, gx = W / tx;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  if (bad) {
+    const hipError_t e = hipMemsetAsync(bad, 0, sizeof(int) * gy * gx, st);
+    if (e != hipSuccess) return -(int)e;
+  }
+  const bool vec = tx % 4 == 0 && W % 4 == 0 && (size_t)ty * (tx / 4) <= (size_t)1024 * kNormKR &&
+                   ((uintptr_t)region & 15) == 0 && ((uintptr_t)tiles & 15) == 0;
+  const dim3 grid(C, gy * gx), block(1024);
+#define SRMI_R2T_NORM(MODE, VEC)                                                                                 \
+  hipLaunchKernelGGL((region_to_tiles_norm_kernel<MODE, VEC>), grid, block, 0, st, region, C, H, W, ty, tx, gx, off, \
+                     dv, tiles, off_out, div_out, bad)
+  if (mode == SRMI_NORM_LSCALE) {
+    if (vec) SRMI_R2T_NORM(SRMI_NORM_LSCALE, true);
+    else SRMI_R2T_NORM(SRMI_NORM_LSCALE, false);
+  } else {
+    if (vec) SRMI_R2T_NORM(SRMI_NORM_AFFINE, true);
+    else SRMI_R2T_NORM(SRMI_NORM_AFFINE, false);
+  }
+#undef SRMI_R2T_NORM
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------ dataset tile statistics
+// _compute_normalization (raw.py:89-106) walks every (tile, variable) plane of every
+// time slice on the host: NormData.add_entry (raw.py:55-60) appends the plane's mean
+// and variance and folds its max and min.  Here one workgroup owns one plane of the
+// [n][C][ty][tx] tensor srmi.llc.get_tiles returns: the plane is read from HBM once
+// (float4) and held in registers, mean and the 2-pass variance (ddof 0) are fp64
+// fixed-order block reductions (as batch_prep_kernel, and for its reason), and the
+// owner adds them to its acc row {sum of means, sum of variances, max, min} with plain
+// stores: no atomics, so the result does not depend on the schedule.  The plane index
+// is on grid.x (a time slice at 16^2 tiles has ~875 000 planes).
+template <int kThreads>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  constexpr int kW = kThreads / 64;
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < kW; ++i) s += red[i];
+  __syncthreads();
+  return s;
+}
+
+__device__ __forceinline__ void tile_stats_commit(double* __restrict__ a, int first, double m, double var, float mn,
+                                                  float mx) {
+  // first: the row is initialised (max from -inf, min from +inf), whatever it held
+  a[0] = first ? m : a[0] + m;
+  a[1] = first ? var : a[1] + var;
+  a[2] = first ? (double)mx : fmax(a[2], (double)mx);
+  a[3] = first ? (double)mn : fmin(a[3], (double)mn);
+}
+
+// n4 = plane elements / 4 <= kThreads * kPer
+template <int kThreads, int kPer>
+__global__ void __launch_bounds__(kThreads) tile_stats_reg_kernel(const float* __restrict__ tiles, int n4,
+                                                                  double* __restrict__ acc, int first) {
+  __shared__ double red[kThreads / 64];
+  __shared__ float redf[2 * kThreads / 64];
+  const size_t p = blockIdx.x;
+  const float4* src = reinterpret_cast<const float4*>(tiles + p * 4 * n4);
+  float4 v[kPer];
+  double s = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int i = threadIdx.x + j * kThreads;
+    if (i < n4) {
+      v[j] = src[i];
+      s += ((double)v[j].x + (double)v[j].y) + ((double)v[j].z + (double)v[j].w);
+      mn = fminf(fminf(mn, v[j].x), fminf(v[j].y, fminf(v[j].z, v[j].w)));
+      mx = fmaxf(fmaxf(mx, v[j].x), fmaxf(v[j].y, fmaxf(v[j].z, v[j].w)));
+    }
+  }
+  const double nn = 4.0 * (double)n4;
+  const double m = block_sum_f64<kThreads>(s, red) / nn;
+  double q = 0.0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    if (threadIdx.x + j * kThreads < n4) {
+      const double a = (double)v[j].x - m, b = (double)v[j].y - m, c = (double)v[j].z - m, d = (double)v[j].w - m;
+      q += (a * a + b * b) + (c * c + d * d);
+    }
+  }
+  const double var = block_sum_f64<kThreads>(q, red) / nn;
+  block_minmax<kThreads>(mn, mx, redf);
+  if (threadIdx.x == 0) tile_stats_commit(acc + p * 4, first, m, var, mn, mx);
+}
+
+// any plane size or alignment: scalar loads, the variance pass re-reads the plane (L2)
+__global__ void __launch_bounds__(256) tile_stats_kernel(const float* __restrict__ tiles, int n,
+                                                         double* __restrict__ acc, int first) {
+  __shared__ double red[4];
+  __shared__ float redf[8];
+  const size_t p = blockIdx.x;
+  const float* src = tiles + p * n;
+  double s = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float a = src[i];
+    s += (double)a;
+    mn = fminf(mn, a);
+    mx = fmaxf(mx, a);
+  }
+  const double m = block_sum_f64<256>(s, red) / (double)n;
+  double q = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double d = (double)src[i] - m;
+    q += d * d;
+  }
+  const double var = block_sum_f64<256>(q, red) / (double)n;
+  block_minmax<256>(mn, mx, redf);
+  if (threadIdx.x == 0) tile_stats_commit(acc + p * 4, first, m, var, mn, mx);
+}
+
+int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first,
+                      hipStream_t st) {
+  if (n < 1 || C < 1 || ty < 1 || tx < 1 || n * C > 0x7fffffffLL || (long long)ty * tx > 0x7fffffffLL)
+    return SRMI_ERR_SHAPE;
+  if (!tiles || !acc) return SRMI_ERR_ARG;
+  const int ne = ty * tx, n4 = ne / 4;
+  const dim3 grid((unsigned)(n * C));
+  if (ne % 4 || ((uintptr_t)tiles & 15) || n4 > 1024 * kNormKR)
+    hipLaunchKernelGGL(tile_stats_kernel, grid, dim3(256), 0, st, tiles, ne, acc, first);
+  else if (n4 <= 64 * 4)  // up to 32^2: one wave per plane
+    hipLaunchKernelGGL((tile_stats_reg_kernel<64, 4>), grid, dim3(64), 0, st, tiles, n4, acc, first);
+  else if (n4 <= 256 * 4)  // up to 64^2
+    hipLaunchKernelGGL((tile_stats_reg_kernel<256, 4>), grid, dim3(256), 0, st, tiles, n4, acc, first);
+  else  // up to 192^2
+    hipLaunchKernelGGL((tile_stats_reg_kernel<1024, kNormKR>), grid, dim3(1024), 0, st, tiles, n4, acc, first);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// get_norm_stats (raw.py:62-63): row (tile, channel) -> {mean of the means, mean of
+// the variances, max, min}, the reference's STATS order
+__global__ void __launch_bounds__(256) tile_stats_rows_kernel(const double* __restrict__ acc, long long rows,
+                                                              double ntimes, float* __restrict__ tstats) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const double* a = acc + r * 4;
+  *reinterpret_cast<float4*>(tstats + r * 4) =
+      make_float4((float)(a[0] / ntimes), (float)(a[1] / ntimes), (float)a[2], (float)a[3]);
+}
+
+// globalize_norm (raw.py:23-30) of channel c = blockIdx.x: each thread folds its tiles
+// t = tid, tid + 1024, ... in order, then fixed-order block reductions.  One workgroup
+// (one CU) per channel walks all n rows at a stride of C * 32 bytes: 28 MB at the
+// 874 800 tiles of an LLC4320 time slice at 16^2.  It runs once per dataset and keeps
+// the order fixed; its time at that size was not measured.
+__global__ void __launch_bounds__(1024) tile_stats_global_kernel(const double* __restrict__ acc, long long n, int C,
+                                                                 double ntimes, float* __restrict__ gstats) {
+  __shared__ double red[16];
+  __shared__ float redf[32];
+  const int c = blockIdx.x;
+  double sm = 0.0, sv = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+  for (long long t = threadIdx.x; t < n; t += 1024) {
+    const double* a = acc + (t * C + c) * 4;
+    sm += a[0] / ntimes;
+    sv += a[1] / ntimes;
+    mx = fmaxf(mx, (float)a[2]);  // max / min are fp32 values held in fp64: exact
+    mn = fminf(mn, (float)a[3]);
+  }
+  sm = block_sum_f64<1024>(sm, red);
+  sv = block_sum_f64<1024>(sv, red);
+  block_minmax<1024>(mn, mx, redf);
+  if (threadIdx.x == 0)
+    *reinterpret_cast<float4*>(gstats + 4 * c) = make_float4((float)(sm / (double)n), (float)(sv / (double)n), mx, mn);
+}
+
+int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
+                               hipStream_t st) {
+  if (n < 1 || C < 1 || ntimes < 1 || n * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (!acc || ((uintptr_t)tstats & 15) || ((uintptr_t)gstats & 15)) return SRMI_ERR_ARG;
+  if (tstats)
+    hipLaunchKernelGGL(tile_stats_rows_kernel, dim3((unsigned)((n * C + 255) / 256)), dim3(256), 0, st, acc, n * C,
+                       (double)ntimes, tstats);
+  if (gstats)
+    hipLaunchKernelGGL(tile_stats_global_kernel, dim3(C), dim3(1024), 0, st, acc, n, C, (double)ntimes, gstats);
   SRMI_CHECK_LAUNCH();
   return 0;
 }

@@ -25,6 +25,9 @@ SRMI_LOSS_RMSE = 0
 SRMI_LOSS_MEAN = 1
 SRMI_INTERP_BILINEAR = 1
 SRMI_INTERP_BICUBIC = 2
+SRMI_NORM_LNORM = 0
+SRMI_NORM_LSCALE = 1
+SRMI_NORM_AFFINE = 2
 # srmi_engine_buffer's `which` (SRMI_BUF_*)
 BUFFERS = {"X0F": 0, "HB": 1, "T": 2, "U": 3, "REC": 4, "BREC": 5, "DU": 6, "DZ": 7, "DRESF": 8, "GROUP_IN_GRAD": 9,
            "RESB": 10, "PS": 11}
@@ -108,6 +111,12 @@ _SIGS = {
     "srmi_region_to_tiles": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P], C.c_int),
     "srmi_tiles_to_region": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "srmi_batch_prep": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P], C.c_int),
+    "srmi_batch_prep_norm": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P],
+                             C.c_int),
+    "srmi_region_to_tiles_norm": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P],
+                                  C.c_int),
+    "srmi_tile_stats": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, P, C.c_int, P], C.c_int),
+    "srmi_tile_stats_finalize": ([P, C.c_longlong, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_llc_index_map_workspace": ([C.c_longlong, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_llc_index_map": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, C.c_size_t, P],
                            C.c_int),

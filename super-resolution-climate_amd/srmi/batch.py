@@ -15,11 +15,14 @@ The reference prepares every training batch on the host in xarray:
 ``prep_batch`` does the three in one HIP kernel (``srmi_batch_prep``, tiles.hip):
 one HBM read of the raw tiles, one write of the HR target and of the LR input.
 The flip index is drawn on the host exactly as the reference draws it.
+
+The other five ``task.norm`` modes (raw.py:182-209) go through
+``srmi_batch_prep_norm`` (``prep_batch(norm=...)``, srmi.norm).
 """
 from __future__ import annotations
 
 import random
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -36,11 +39,25 @@ def xyflip_index(enabled: bool, rng: Optional[random.Random] = None) -> int:
 
 def prep_batch(raw: torch.Tensor, flip_index: int = 0, scale: int = 4, with_lr: bool = True,
                hr: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None,
-               stream=None) -> Dict[str, torch.Tensor]:
+               stream=None, norm: str = "lnorm", stats=None,
+               tile_range: Optional[Tuple[int, int]] = None) -> Dict[str, torch.Tensor]:
     """raw [B, C, T, T] fp32 device tiles -> {'hr': xyflip(lnorm(raw)), 'lr':
     downsample(hr, scale), 'mean': [B, C, 1, 1], 'std': [B, C, 1, 1],
     'xyflip': flip_index}.  Raises SrmiError on bad shapes (T odd, T % scale,
-    flip_index outside 0..7)."""
+    flip_index outside 0..7).
+
+    norm: task.norm (srmi.norm.NORM_TYPES; anything else raises the reference's
+    ``Exception("Unknown norm: ...")``).  The statistics returned are the ones the
+    reference's norm() puts in attrs (raw.py:169-214): 'mean' / 'std' for lnorm and
+    tnorm, 'max' / 'min' for lscale and tscale, none for gnorm and gscale.  The
+    dataset modes (gnorm, gscale, tnorm, tscale) need ``stats``, a finalised
+    srmi.norm.NormStats (ValueError without), and tnorm / tscale the batch's
+    ``tile_range`` (start, end) in the time slice, default (0, B); tscale takes its
+    rows positionally, as tnorm does (srmi.norm's docstring)."""
+    if norm != "lnorm":
+        from .norm import DATASET_NORMS, check_norm
+        if check_norm(norm) in DATASET_NORMS and stats is None:
+            raise ValueError(f"prep_batch: norm {norm!r} needs the dataset statistics (stats=NormStats)")
     if raw.dtype != torch.float32 or raw.dim() != 4 or not raw.is_contiguous():
         raise ValueError("prep_batch: raw must be a contiguous fp32 [B, C, T, T] tensor")
     B, C, T, T2 = raw.shape
@@ -50,6 +67,13 @@ def prep_batch(raw: torch.Tensor, flip_index: int = 0, scale: int = 4, with_lr: 
         hr = torch.empty_like(raw)
     if with_lr and lr is None:
         lr = torch.empty(B, C, T // scale, T // scale, device=raw.device, dtype=torch.float32)
+    if norm != "lnorm":
+        from .norm import prep_norm
+        out = {"hr": hr, "xyflip": int(flip_index)}
+        out.update(prep_norm(raw, norm, flip_index, scale, hr, lr if with_lr else None, stats, tile_range, stream))
+        if with_lr:
+            out["lr"] = lr
+        return out
     mean = torch.empty(B, C, 1, 1, device=raw.device, dtype=torch.float32)
     std = torch.empty_like(mean)
     call("srmi_batch_prep", ptr(raw), B, C, T, int(flip_index), int(scale), ptr(hr),

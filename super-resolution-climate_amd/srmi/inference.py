@@ -4,7 +4,8 @@ and ModelTrainer.evaluate.
 Reference (sres/controller/dual_trainer.py:396-543, sres/base/source/swot/raw.py:169-233):
 a region [C, H, W] is cut floor-wise into a gy x gx grid of HR tiles (tile id =
 y * gx + x), tiles holding a non-finite value are dropped, every tile/channel is
-'lnorm'-normalised (mean/std over the tile, ddof 0), the LR input is the bicubic
+normalised by task.norm ('lnorm': mean/std over the tile, ddof 0; the other five
+modes: srmi.norm), the LR input is the bicubic
 1/s of the tile (apply_network, :557-571), the model output and the bicubic
 interpolation baseline (upsample) are scored against the tile in batches of
 task.batch_size tiles (TileBatchIterator, sres/data/tiles.py:48-74) with
@@ -63,9 +64,17 @@ class TiledInference:
     def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw: Tuple[int, int, int],
                  tile_hr: Tuple[int, int] = (192, 192), device: Optional[torch.device] = None, graph: bool = True,
                  micro: Optional[int] = None, batch_size: int = 36, loss_fn: str = "l2",
-                 info: Optional[DistInfo] = None, task=None):
+                 info: Optional[DistInfo] = None, task=None, norm: Optional[str] = None, stats=None):
         """batch_size: task.batch_size (the tiles scored per batch; 36 in every
         reference task yaml); loss_fn: model.loss_fn.
+
+        norm: task.norm (srmi.norm.NORM_TYPES); None reads it from the task ('lnorm'
+        without one).  The dataset modes (gnorm, gscale, tnorm, tscale) take ``stats``,
+        a srmi.norm.NormStats with one row per GRID CELL (NormStats.for_grid).  The
+        mosaics follow denorm (dual_trainer.py:67-77): lnorm / tnorm tiles are
+        de-normalised with mean / std, lscale / tscale with min / max - min, and gnorm /
+        gscale tiles stay normalised (norm() records no statistics for them,
+        raw.py:187-195, so the reference's denorm does nothing).
 
         info (world > 1): multi-rank inference: the region's tile
         grid is dealt round-robin over the ranks (rank r runs grid tiles r, r + W,
@@ -81,6 +90,12 @@ class TiledInference:
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
         from .config import data_downsample_factor, interp_mode
+        from .norm import ATTR_KEYS, DATASET_NORMS, MODES, check_norm, norm_type
+        self.norm = check_norm(norm) if norm is not None else norm_type(task)
+        if self.norm in DATASET_NORMS and stats is None:
+            raise ValueError(f"norm {self.norm!r} needs the dataset statistics (stats=NormStats.for_grid(...))")
+        self.norm_mode = MODES[self.norm]
+        self.denorm = bool(ATTR_KEYS[self.norm])  # gnorm / gscale mosaics stay normalised
         # apply_network's pre-downsampling (:561-563): the normalised tiles are scored
         # at 1/ds of the tile size (target, model, interpolated and their mosaics)
         self.ds = data_downsample_factor(task)
@@ -121,6 +136,15 @@ class TiledInference:
         self.tiles0 = torch.empty((n, C, ty0, tx0), **f32) if self.ds > 1 else self.tiles
         self.mean = torch.empty((n, C), **f32)
         self.std = torch.empty((n, C), **f32)
+        if self.norm in DATASET_NORMS:
+            # filled once, before any capture: the tiling kernel reads them as offset and
+            # divisor, and the mosaics as mean and std (x * div + off undoes both branches)
+            off, div = stats.offsets(self.norm, (0, n))
+            if tuple(off.shape) != (n, C):
+                raise ValueError(f"stats hold {tuple(off.shape)} rows, the grid has {n} cells x {C} channels "
+                                 "(NormStats.for_grid)")
+            self.mean.copy_(off)
+            self.std.copy_(div)
         self.bad = torch.zeros(n, dtype=torch.int32, device=d)
         self.lr = torch.empty((n, C, ty // s, tx // s), **f32)
         self.sr = torch.empty((n, C, ty, tx), **f32)
@@ -174,8 +198,13 @@ class TiledInference:
     # ---------------------------------------------------------------- pieces
     def _tile(self):
         st = stream_handle()
-        call("srmi_region_to_tiles", ptr(self.region), self.C, self.H, self.W, self.ty0, self.tx0, ptr(self.tiles0),
-             ptr(self.mean), ptr(self.std), ptr(self.bad), st)
+        if self.norm == "lnorm":
+            call("srmi_region_to_tiles", ptr(self.region), self.C, self.H, self.W, self.ty0, self.tx0,
+                 ptr(self.tiles0), ptr(self.mean), ptr(self.std), ptr(self.bad), st)
+        else:  # lscale writes min / max - min into mean / std; the dataset modes read them
+            call("srmi_region_to_tiles_norm", ptr(self.region), self.C, self.H, self.W, self.ty0, self.tx0,
+                 self.norm_mode, ptr(self.mean), ptr(self.std), ptr(self.tiles0), ptr(self.mean), ptr(self.std),
+                 ptr(self.bad), st)
         if self.ds > 1:  # apply_network: downsample(input, scale_factor=ds) of the normalised tiles
             downsample(self.tiles0, self.ds, out=self.tiles, mode=self.dmode)
 
@@ -207,8 +236,8 @@ class TiledInference:
         C, gy, gx, s = self.C, self.gy, self.gx, self.s
         for name, src, ty, tx in (("input", lr, self.ty // s, self.tx // s), ("target", tiles, self.ty, self.tx),
                                   ("interpolated", interp, self.ty, self.tx), ("model", sr, self.ty, self.tx)):
-            call("srmi_tiles_to_region", ptr(src), ptr(mean), ptr(std), ptr(inv), C, ty, tx, gy, gx,
-                 ptr(self.images[name]), st)
+            call("srmi_tiles_to_region", ptr(src), ptr(mean) if self.denorm else None, ptr(std), ptr(inv), C, ty, tx,
+                 gy, gx, ptr(self.images[name]), st)
 
     def _all_tiles(self):
         self._kept_tiles = self.tiles
@@ -413,8 +442,8 @@ class TiledInference:
         C, gy, gx, s = self.C, self.gy, self.gx, self.s
         for name, src, ty, tx in (("input", self.lr, self.ty // s, self.tx // s), ("target", tiles, self.ty, self.tx),
                                   ("interpolated", self.interp, self.ty, self.tx), ("model", self.sr, self.ty, self.tx)):
-            call("srmi_tiles_to_region", ptr(src), ptr(mean), ptr(std), ptr(inv), C, ty, tx, gy, gx,
-                 ptr(self.images[name]), st)
+            call("srmi_tiles_to_region", ptr(src), ptr(mean) if self.denorm else None, ptr(std), ptr(inv), C, ty, tx,
+                 gy, gx, ptr(self.images[name]), st)
 
     def _run_compacted(self):
         keep = torch.nonzero(self.bad == 0).flatten()

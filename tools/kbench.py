@@ -17,7 +17,7 @@ if os.environ.get("KBENCH_STAMPS"):  # phase stamps live only in the diagnostic 
 
 import torch  # noqa: E402
 
-from srmi._lib import call, ptr  # noqa: E402
+from srmi._lib import SRMI_NORM_AFFINE, SRMI_NORM_LSCALE, call, ptr  # noqa: E402
 
 
 def timeit(fn, iters):
@@ -31,6 +31,29 @@ def timeit(fn, iters):
     e1.record(st)
     e1.synchronize()
     return e0.elapsed_time(e1) * 1000.0 / iters  # us
+
+
+def timeit_each(fns, iters):
+    """{name: fn} launched in turn, iters rounds, every launch between its own pair of
+    events: {name: us_median, us_min, us_max} (the spread of one run, same box, same
+    clocks -- what a comparison between the entries can be held to)."""
+    st = torch.cuda.current_stream()
+    for _ in range(3):
+        for fn in fns.values():
+            fn()
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+          for k in fns}
+    for i in range(iters):
+        for k, fn in fns.items():
+            ev[k][i][0].record(st)
+            fn()
+            ev[k][i][1].record(st)
+    torch.cuda.synchronize()
+    out = {}
+    for k in fns:
+        us = sorted(a.elapsed_time(b) * 1000.0 for a, b in ev[k])
+        out[k] = {"us_median": round(us[len(us) // 2], 2), "us_min": round(us[0], 2), "us_max": round(us[-1], 2)}
+    return out
 
 
 def main():
@@ -120,6 +143,39 @@ def main():
         call("srmi_batch_prep", ptr(raw), N, Cb, T, 5, 4, ptr(hrb), ptr(lrb), ptr(mb), ptr(sb), S())
     us = timeit(prep, args.iters)
     res["batch_prep"] = {"us": round(us, 2), "GBps": round(raw.numel() * 4 * (2 + 1 / 16) / us / 1e3, 1)}
+    # the other task.norm modes (srmi.norm) beside 'lnorm' (prep, above): the three are
+    # launched in turn, every launch timed by its own event pair -> median and spread
+    offb, divb = torch.full((N, Cb), 280.0, device=d), torch.full((N, Cb), 1.25, device=d)
+
+    def prep_norm(mode):
+        def f():
+            call("srmi_batch_prep_norm", ptr(raw), N, Cb, T, 5, 4, mode, ptr(offb), ptr(divb), ptr(hrb), ptr(lrb),
+                 ptr(mb), ptr(sb), S())
+        return f
+    # prep_batch(norm='lscale') returns the tile's exact max, which it takes from one
+    # srmi_tile_stats launch over the batch after the kernel: the pair is what that call costs
+    accb = torch.empty(N, Cb, 4, dtype=torch.float64, device=d)
+    lscale = prep_norm(SRMI_NORM_LSCALE)
+
+    def lscale_with_max():
+        lscale()
+        call("srmi_tile_stats", ptr(raw), N, Cb, T, T, ptr(accb), 1, S())
+    prep_bytes = raw.numel() * 4 * (2 + 1 / 16)
+    # "batch_prep" above is the same kernel timed back to back (the figure of earlier
+    # rounds); "@same_run" entries are the ones to compare with each other
+    for k, v in timeit_each({"batch_prep": prep, "batch_prep_norm_affine": prep_norm(SRMI_NORM_AFFINE),
+                             "batch_prep_norm_lscale": lscale,
+                             "batch_prep_norm_lscale+tile_stats": lscale_with_max}, args.iters).items():
+        res[k + "@same_run"] = dict(v, GBps=round(prep_bytes / v["us_median"] / 1e3, 1))
+    # dataset tile statistics (srmi_tile_stats): one read of the tiles
+    for n, Cs, Ts in ((441, 1, 192), (2205, 2, 48)):
+        tl = torch.randn(n, Cs, Ts, Ts, device=d) + 280.0
+        acc = torch.empty(n, Cs, 4, dtype=torch.float64, device=d)
+
+        def stats():
+            call("srmi_tile_stats", ptr(tl), n, Cs, Ts, Ts, ptr(acc), 1, S())
+        v = timeit_each({"s": stats}, args.iters)["s"]
+        res[f"tile_stats_{n}x{Cs}x{Ts}x{Ts}"] = dict(v, GBps=round(tl.numel() * 4 / v["us_median"] / 1e3, 1))
     print(json.dumps(res, indent=1))
 
 
