@@ -460,6 +460,32 @@ int srmi_tiles_nonfinite(const float* region, int C, int H, int W, int ty, int t
 int srmi_tiles_gather(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
                       float* out, void* stream);
 
+/* Sparse reads of a wet-value file (SWOTRawDataLoader.load_file, raw.py:133-145,
+ * reads the whole file; a ROI needs a small share of it).  The file is cut into
+ * blocks of 2^block_shift words.  mask[n_blocks] (int32) is zeroed, then
+ * mask[idx >> block_shift] = 1 for every idx_map entry >= 0.  SRMI_ERR_SHAPE if
+ * an index lies past n_blocks << block_shift.  Once per template and ROI;
+ * synchronises the stream (the error comes back from the device). */
+int srmi_llc_block_mask(const int* idx_map, long long npix, int block_shift, int* mask, int n_blocks, void* stream);
+/* load_file (raw.py:133-145) over the blocks that were read: block_base[b] = the
+ * word offset of file block b in the compact staging buffer, -1 = not read.
+ * idx_out[p] = idx < 0 ? -1 : block_base[idx >> shift] + (idx & (2^shift - 1)),
+ * and -1 where the block was not read: srmi_llc_gather(data = the compact words,
+ * n_values = their count, idx_map = idx_out) then gives the ROI image, NaN there.
+ * Once per template and ROI. */
+int srmi_llc_compact_map(const int* idx_map, long long npix, int block_shift, const int* block_base, int n_blocks,
+                         int* idx_out, void* stream);
+/* get_tiles' keep list (raw.py:216-233) on the device: keep = flatnonzero(bad == 0)
+ * over the C * ncells flags of srmi_tiles_nonfinite, n = len(keep) / C;
+ * src[0 .. n*C) = keep[0 .. n*C), count[0] = n, count[1] = len(keep).  An
+ * order-preserving compaction by one workgroup, no atomics: deterministic. */
+int srmi_tiles_keep(const int* bad, int C, int ncells, int* src, int* count, void* stream);
+/* srmi_tiles_gather (get_tiles, raw.py:216-233) with the slot count count[0] * C
+ * read on the device (srmi_tiles_keep's count): launched for max_slots planes of
+ * out; a plane at or past the count neither reads src nor writes out. */
+int srmi_tiles_gather_dev(const float* region, int C, int H, int W, int ty, int tx, const int* src, const int* count,
+                          int max_slots, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1572,6 +1572,24 @@ int srmi_tiles_gather(const float* region, int C, int H, int W, int ty, int tx, 
   return tiles_gather_launch(region, C, H, W, ty, tx, src, nslots, out, S_(stream));
 }
 
+int srmi_llc_block_mask(const int* idx_map, long long npix, int block_shift, int* mask, int n_blocks, void* stream) {
+  return llc_block_mask_launch(idx_map, npix, block_shift, mask, n_blocks, S_(stream));
+}
+
+int srmi_llc_compact_map(const int* idx_map, long long npix, int block_shift, const int* block_base, int n_blocks,
+                         int* idx_out, void* stream) {
+  return llc_compact_map_launch(idx_map, npix, block_shift, block_base, n_blocks, idx_out, S_(stream));
+}
+
+int srmi_tiles_keep(const int* bad, int C, int ncells, int* src, int* count, void* stream) {
+  return tiles_keep_launch(bad, C, ncells, src, count, S_(stream));
+}
+
+int srmi_tiles_gather_dev(const float* region, int C, int H, int W, int ty, int tx, const int* src, const int* count,
+                          int max_slots, float* out, void* stream) {
+  return tiles_gather_dev_launch(region, C, H, W, ty, tx, src, count, max_slots, out, S_(stream));
+}
+
 int srmi_batch_prep(const float* raw, int B, int C, int T, int flip_index, int scale, float* hr, float* lr,
                     float* mean, float* std, void* stream) {
   return batch_prep_launch(raw, B, C, T, flip_index, scale, hr, lr, mean, std, S_(stream));

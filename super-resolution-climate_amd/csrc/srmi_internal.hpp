@@ -270,6 +270,13 @@ int llc_gather_launch(const uint32_t* data, long long nvals, const int* idx, lon
 int tiles_nonfinite_launch(const float* region, int C, int H, int W, int ty, int tx, int* bad, hipStream_t st);
 int tiles_gather_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
                         float* out, hipStream_t st);
+// sparse file reads and the device keep list of the time-slice feed (tiles.hip)
+int llc_block_mask_launch(const int* idx, long long np, int shift, int* mask, int n_blocks, hipStream_t st);
+int llc_compact_map_launch(const int* idx, long long np, int shift, const int* base, int n_blocks, int* out,
+                           hipStream_t st);
+int tiles_keep_launch(const int* bad, int C, int ncells, int* src, int* count, hipStream_t st);
+int tiles_gather_dev_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src,
+                            const int* count, int max_slots, float* out, hipStream_t st);
 int batch_prep_launch(const float* raw, int B, int C, int T, int flip, int scale, float* hr, float* lr, float* mean,
                       float* stdv, hipStream_t st);
 // the other task.norm modes and the dataset tile statistics (tiles.hip)

@@ -983,4 +983,157 @@ int tiles_gather_launch(const float* region, int C, int H, int W, int ty, int tx
   return 0;
 }
 
+// ------------------------------------------------- sparse file reads (srmi.feed)
+// A ROI touches a small share of a wet-value file.  The file is cut into blocks of
+// 2^shift words; block_mask marks the blocks the ROI's index map touches (the host
+// then reads only those, back to back, into a compact staging buffer) and
+// compact_map rewrites the index map into that buffer.  Both run once per
+// template and ROI; every file is then llc_gather_kernel on the compact words.
+// err[0] is set when an index lies past the n_blocks blocks (never stored through).
+__global__ void __launch_bounds__(256) llc_block_mask_kernel(const int* __restrict__ idx, long long np, int shift,
+                                                             int* __restrict__ mask, int n_blocks,
+                                                             int* __restrict__ err) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= np) return;
+  const int i = idx[p];
+  if (i < 0) return;
+  const int b = i >> shift;
+  if (b < n_blocks) mask[b] = 1;  // every writer stores the same value
+  else err[0] = 1;
+}
+
+int llc_block_mask_launch(const int* idx, long long np, int shift, int* mask, int n_blocks, hipStream_t st) {
+  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
+  if (!idx || !mask) return SRMI_ERR_ARG;
+  int* err = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int));
+  if (e != hipSuccess) return -(int)e;
+  int herr = 0;
+  e = hipMemsetAsync(err, 0, sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(mask, 0, sizeof(int) * (size_t)n_blocks, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(llc_block_mask_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
+                       mask, n_blocks, err);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(err);
+  if (e != hipSuccess) return -(int)e;
+  return herr ? SRMI_ERR_SHAPE : 0;
+}
+
+// out[p] = block_base[idx >> shift] + (idx & (2^shift - 1)); -1 for land, for a
+// block that is not read (base -1) and for an index past the blocks
+__global__ void __launch_bounds__(256) llc_compact_map_kernel(const int* __restrict__ idx, long long np, int shift,
+                                                              const int* __restrict__ base, int n_blocks,
+                                                              int* __restrict__ out) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= np) return;
+  const int i = idx[p];
+  int o = -1;
+  if (i >= 0 && (i >> shift) < n_blocks) {
+    const int b = base[i >> shift];
+    if (b >= 0) o = b + (i & ((1 << shift) - 1));
+  }
+  out[p] = o;
+}
+
+int llc_compact_map_launch(const int* idx, long long np, int shift, const int* base, int n_blocks, int* out,
+                           hipStream_t st) {
+  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
+  if (!idx || !base || !out) return SRMI_ERR_ARG;
+  hipLaunchKernelGGL(llc_compact_map_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
+                     base, n_blocks, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// get_tiles' keep list on the device: keep = flatnonzero(bad == 0), n = len(keep) / C,
+// src = keep[:n * C] (srmi.llc.get_tiles).  ONE workgroup: a first pass counts the kept
+// flags (so nothing past n * C is stored), a second walks them in chunks of
+// kKeepThreads with a wave inclusive scan + wave offsets (as llc_rank_kernel) and
+// carries the running offset from chunk to chunk.  Fixed order, no atomics.
+constexpr int kKeepThreads = 1024;
+
+__global__ void __launch_bounds__(kKeepThreads) tiles_keep_kernel(const int* __restrict__ bad, int C, int total,
+                                                                  int* __restrict__ src, int* __restrict__ count) {
+  __shared__ int wsum[kKeepThreads / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int c = 0;
+  for (int i = threadIdx.x; i < total; i += kKeepThreads) c += bad[i] == 0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) wsum[w] = c;
+  __syncthreads();
+  int nkeep = 0;
+  for (int i = 0; i < kKeepThreads / 64; ++i) nkeep += wsum[i];
+  __syncthreads();
+  const int n = nkeep / C, nsrc = n * C;
+  if (threadIdx.x == 0) {
+    count[0] = n;
+    count[1] = nkeep;
+  }
+  int run = 0;
+  for (int a = 0; a < total && run < nsrc; a += kKeepThreads) {  // (run is uniform over the block)
+    const int i = a + threadIdx.x;
+    const int k = i < total && bad[i] == 0;
+    int inc = k;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int woff = 0, tot = 0;
+    for (int j = 0; j < kKeepThreads / 64; ++j) {
+      woff += j < w ? wsum[j] : 0;
+      tot += wsum[j];
+    }
+    const int pos = run + woff + inc - k;
+    if (k && pos < nsrc) src[pos] = i;
+    run += tot;
+    __syncthreads();
+  }
+}
+
+int tiles_keep_launch(const int* bad, int C, int ncells, int* src, int* count, hipStream_t st) {
+  if (C < 1 || ncells < 1 || (long long)C * ncells > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (!bad || !src || !count) return SRMI_ERR_ARG;
+  hipLaunchKernelGGL(tiles_keep_kernel, dim3(1), dim3(kKeepThreads), 0, st, bad, C, C * ncells, src, count);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// tiles_gather_kernel with the slot count on the device (count[0] * C, tiles_keep's
+// result): launched for max_slots planes, a plane at or past the count returns
+// before it reads src or writes out.  grid (max_slots, ceil(ty*tx/1024))
+__global__ void __launch_bounds__(256) tiles_gather_dev_kernel(const float* __restrict__ region, int C, int H, int W,
+                                                               int ty, int tx, int gx, int ntile,
+                                                               const int* __restrict__ src,
+                                                               const int* __restrict__ count,
+                                                               float* __restrict__ out) {
+  const int m = blockIdx.x;
+  if (m >= count[0] * C) return;
+  const int j = src[m];
+  const int c = j / ntile, t = j - c * ntile;
+  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  const float* s = region + (size_t)c * H * W + (size_t)y0 * W + x0;
+  float* d = out + (size_t)m * ty * tx;
+  for (int i = blockIdx.y * 1024 + threadIdx.x; i < min(ty * tx, (int)(blockIdx.y + 1) * 1024); i += 256)
+    d[i] = s[(size_t)(i / tx) * W + (i % tx)];
+}
+
+int tiles_gather_dev_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src,
+                            const int* count, int max_slots, float* out, hipStream_t st) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx || max_slots < 0) return SRMI_ERR_SHAPE;
+  if ((long long)ty * tx > 65535LL * 1024) return SRMI_ERR_SHAPE;  // grid.y
+  if (max_slots == 0) return 0;
+  if (!region || !src || !count || !out) return SRMI_ERR_ARG;
+  const int gx = W / tx, ntile = (H / ty) * gx;
+  hipLaunchKernelGGL(tiles_gather_dev_kernel, dim3(max_slots, (ty * tx + 1023) / 1024), dim3(256), 0, st, region, C, H,
+                     W, ty, tx, gx, ntile, src, count, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace srmi

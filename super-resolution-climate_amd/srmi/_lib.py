@@ -123,6 +123,10 @@ _SIGS = {
     "srmi_llc_gather": ([P, C.c_longlong, P, C.c_longlong, P, P], C.c_int),
     "srmi_tiles_nonfinite": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "srmi_tiles_gather": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P], C.c_int),
+    "srmi_llc_block_mask": ([P, C.c_longlong, C.c_int, P, C.c_int, P], C.c_int),
+    "srmi_llc_compact_map": ([P, C.c_longlong, C.c_int, P, C.c_int, P, P], C.c_int),
+    "srmi_tiles_keep": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
+    "srmi_tiles_gather_dev": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

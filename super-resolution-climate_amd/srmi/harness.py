@@ -192,7 +192,9 @@ def batch_starts(ntiles: int, batch_size: int, randomize: bool, rng: Optional[ra
 def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], nepochs: int, batch_size: int,
                      store: Optional[CheckpointStore] = None, records: Optional[LossRecords] = None,
                      refresh_state: bool = False, rng: Optional[random.Random] = None,
-                     on_epoch_end: Optional[Callable[[int, float], None]] = None) -> Dict[str, float]:
+                     on_epoch_end: Optional[Callable[[int, float], None]] = None,
+                     prepare: Optional[Callable[[torch.Tensor, int, int, int], torch.Tensor]] = None,
+                     xyflip: bool = False) -> Dict[str, float]:
     """ModelTrainer.train (dual_trainer.py:271-347) on the fused step.
 
     timeslices[i]() returns time slice i as normalised HR tiles [ntiles, C, H, W]
@@ -209,7 +211,19 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
     trainer.step(tiles, shard=(t0, gb)), so the loss and gradient scale are those of
     the whole batch (srmi.trainer) and a short last batch of gb < world tiles leaves
     some ranks with none.  trainer.batch must hold ceil(batch_size / world) tiles.
-    Only rank 0 clears, saves and records; a barrier follows each of its writes."""
+    Only rank 0 clears, saves and records; a barrier follows each of its writes.
+
+    prepare (default None: nothing changes, the time slices are already normalised):
+    the reference's per-batch preparation (SRBatch.load_batch, sres/base/source/
+    batch.py:283-301: norm, then one xyflip draw per batch, :37-49).  timeslices[i]()
+    then returns RAW tiles and every step trains prepare(raw_batch, start, gb, flip)
+    -> normalised HR tiles, start = the batch's first tile in the time slice (this
+    rank's first tile, data parallel), gb = the global batch's tiles (srmi.feed's
+    TimesliceFeed.prepare makes one).  Rank 0 draws the time slice's flips with
+    xyflip_index(xyflip, rng) right after the shuffle, one per batch in batch order
+    -- the order one reference process consumes `random` -- and they are broadcast
+    with the starts, so every rank prepares the same flip."""
+    from .batch import xyflip_index
     from .dist import DistInfo, barrier, broadcast_ints, shard_capacity, shard_range
     info = getattr(trainer, "info", None) or DistInfo()
     dev = getattr(trainer, "device", None)
@@ -243,15 +257,21 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
             ntiles = tiles.shape[0]
             nb = len(range(0, ntiles, batch_size))
             starts = batch_starts(ntiles, batch_size, True, rng) if lead else [0] * nb
+            if prepare is not None:  # the flips ride behind the starts in the one broadcast
+                starts = starts + ([xyflip_index(xyflip, rng) for _ in range(nb)] if lead else [0] * nb)
             starts = broadcast_ints(starts, info, dev)  # rank 0's order on every rank
+            starts, flips = starts[:nb], starts[nb:]
             losses, ilosses = [], []
-            for start in starts:
+            for ib, start in enumerate(starts):
                 gb = min(batch_size, ntiles - start)
+                a, e = shard_range(gb, info) if info.enabled else (0, gb)
+                batch = tiles[start + a:start + e]
+                if prepare is not None:
+                    batch = prepare(batch, start + a, gb, flips[ib])
                 if info.enabled:
-                    a, e = shard_range(gb, info)
-                    out = trainer.step(tiles[start + a:start + e], shard=(a, gb))
+                    out = trainer.step(batch, shard=(a, gb))
                 else:
-                    out = trainer.step(tiles[start:start + gb])
+                    out = trainer.step(batch)
                 losses.append(out["loss"].clone())  # (views of the trainer's loss record)
                 ilosses.append(out["interp_loss"].clone())
             # accumulate_loss: mean of the batch losses (one host sync per time slice)

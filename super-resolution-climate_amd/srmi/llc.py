@@ -16,10 +16,17 @@ The host only reads raw file bytes (no decoding); the byte swap, mask
 expansion, face rearrangement and ROI cut are HIP kernels (tiles.hip).  The
 template -> ROI index map is built once per template on the device (mask scan),
 after which each file is one gather.
+
+``LLCSource.read_plan`` is the sparse form of the read for srmi.feed: the file
+blocks the ROI touches (srmi_llc_block_mask), merged into extents on the host
+(``plan_extents``), and the index map into the compact buffer those extents fill
+(srmi_llc_compact_map); ``LLCReadPlan.read_into`` reads them.  ``load_file`` still
+reads whole files.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -83,6 +90,104 @@ class LLCSource:
         for c, pth in enumerate(data_paths):
             self.load_file(pth, out=out[c:c + 1])
         return out
+
+    def read_plan(self, block_words: int = 1024, max_gap_blocks: int = 0) -> "LLCReadPlan":
+        """The file blocks (of block_words words, a power of two) this ROI touches, as
+        extents to read into a compact staging buffer, and the index map into that
+        buffer (srmi_llc_block_mask, plan_extents, srmi_llc_compact_map).  Once per
+        source; load_file's whole-file read stays as it is."""
+        shift = _block_shift(block_words)
+        n_blocks = max(1, -(-self.n_wet // block_words))
+        mask = torch.empty(n_blocks, dtype=torch.int32, device=self.device)
+        st = stream_handle(torch.cuda.current_stream(self.device))
+        npix = self.ys * self.xs
+        call("srmi_llc_block_mask", ptr(self.idx), npix, shift, ptr(mask), n_blocks, st)
+        extents, base, n_words = plan_extents(mask.cpu().numpy(), block_words, max_gap_blocks, self.n_wet)
+        dbase = torch.from_numpy(base).to(self.device)
+        idx = torch.empty(npix, dtype=torch.int32, device=self.device)
+        call("srmi_llc_compact_map", ptr(self.idx), npix, shift, ptr(dbase), n_blocks, ptr(idx), st)
+        return LLCReadPlan(extents, base, n_words, self.n_wet, block_words, idx)
+
+
+def _block_shift(block_words: int) -> int:
+    if block_words < 1 or block_words > 1 << 30 or block_words & (block_words - 1):
+        raise ValueError(f"block_words {block_words} is not a power of two in 1..2^30")
+    return int(block_words).bit_length() - 1
+
+
+def plan_extents(mask, block_words: int, max_gap_blocks: int, n_wet: int):
+    """Host side of the read plan.  mask[b] != 0: file block b (words
+    [b * block_words, (b + 1) * block_words), the last one clipped to n_wet) is
+    needed.  Runs of needed blocks are merged across gaps of at most max_gap_blocks
+    blocks; the gap blocks merged in are read too and get bases of their own.
+
+    -> (extents, block_base, n_words): extents = [(file_word_offset, n_words,
+    staging_word_offset)], ascending and disjoint, the staging offsets their running
+    sum; block_base int32 [len(mask)] = the staging word offset of each block read,
+    -1 for the others; n_words = the words read per file.  ValueError at 2^31
+    words (the compact index map is int32)."""
+    _block_shift(block_words)
+    mask = np.asarray(mask).reshape(-1)
+    nb = mask.size
+    if max_gap_blocks < 0:
+        raise ValueError(f"max_gap_blocks {max_gap_blocks} < 0")
+    if nb != -(-n_wet // block_words) and not (n_wet == 0 and nb == 1):
+        raise ValueError(f"{nb} blocks of {block_words} words do not cover {n_wet} values exactly")
+    base = np.full(nb, -1, dtype=np.int32)
+    need = np.flatnonzero(mask)
+    if need.size == 0:
+        return [], base, 0
+    cut = np.flatnonzero(np.diff(need) - 1 > max_gap_blocks)
+    first = need[np.r_[0, cut + 1]]           # first and last block of every merged run
+    last = need[np.r_[cut, need.size - 1]]
+    off = first.astype(np.int64) * block_words
+    cnt = np.minimum((last.astype(np.int64) + 1) * block_words, n_wet) - off
+    stag = np.cumsum(cnt) - cnt
+    n_words = int(cnt.sum())
+    if n_words >= 1 << 31:
+        raise ValueError(f"the plan reads {n_words} words per file; the compact index map holds 2^31 - 1")
+    for b0, b1, s in zip(first.tolist(), last.tolist(), stag.tolist()):
+        base[b0:b1 + 1] = s + np.arange(b1 - b0 + 1, dtype=np.int64) * block_words
+    extents = [(int(o), int(c), int(s)) for o, c, s in zip(off, cnt, stag)]
+    return extents, base, n_words
+
+
+class LLCReadPlan:
+    """What LLCSource.read_plan returns.  extents / block_base / n_words: see
+    plan_extents; nbytes = the bytes read per file; idx = the device index map into
+    the compact words, for srmi_llc_gather(data = the compact words, n_values =
+    n_words, idx_map = idx)."""
+
+    def __init__(self, extents: List[Tuple[int, int, int]], block_base: np.ndarray, n_words: int, n_wet: int,
+                 block_words: int, idx: Optional[torch.Tensor] = None):
+        self.extents, self.block_base, self.n_words = extents, block_base, int(n_words)
+        self.n_wet, self.block_words, self.idx = int(n_wet), int(block_words), idx
+        self.nbytes = 4 * self.n_words
+
+    def read_into(self, path: str, pinned_words: torch.Tensor) -> None:
+        """The plan's extents of one wet-value file -> pinned_words[:n_words] (a
+        4-byte host tensor, usually pinned), raw bytes, no decoding.  File I/O only:
+        safe in a reader thread."""
+        size = os.path.getsize(path)
+        if size != 4 * self.n_wet:
+            raise ValueError(f"{path}: {size // 4} values for {self.n_wet} wet cells" if size % 4 == 0 else
+                             f"{path}: size {size} is not a multiple of 4 bytes")
+        if pinned_words.element_size() != 4 or pinned_words.numel() < self.n_words or \
+                not pinned_words.is_contiguous() or pinned_words.device.type != "cpu":
+            raise ValueError(f"read_into: need a contiguous host tensor of >= {self.n_words} 4-byte words")
+        buf = memoryview(pinned_words.numpy()).cast("B")
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            for off, cnt, stag in self.extents:
+                a, e, pos = 4 * stag, 4 * (stag + cnt), 4 * off
+                while a < e:
+                    got = os.preadv(fd, [buf[a:e]], pos)
+                    if got <= 0:
+                        raise ValueError(f"{path}: short read at byte {pos}")
+                    a += got
+                    pos += got
+        finally:
+            os.close(fd)
 
 
 def get_tiles(region: torch.Tensor, ty: int, tx: int) -> Tuple[torch.Tensor, np.ndarray, Tuple[int, int]]:
