@@ -96,7 +96,7 @@ __device__ __forceinline__ void ca_scale_load_params(const CaScale& c, CaScalePr
   q.bc2 = c.bc2[c8];
 }
 
-// The partial-mean path (training, SRMI_CA_MPART): conv1's workgroups leave their share of
+// The partial-mean path (training): conv1's workgroups leave their share of
 // the matvec in c.mpart [N][nruns][64]; conv2 issues the first kCaPreStrips of them (and
 // its bias) ahead, in q.tp / q.bcm (channel tid & 63)
 __device__ __forceinline__ void ca_mpart_load(const CaScale& c, int n, CaScalePre& q) {
@@ -121,7 +121,7 @@ __device__ __forceinline__ float sum8(float v) {
 // partials, summed in fixed order), the border-line sums bs (row 0, row H-1, column 0,
 // column W-1) and the corners cn ((0,0) (0,W-1) (H-1,0) (H-1,W-1)), each [64] in LDS;
 // wv: the lane's slices of conv2's bf16 filter image (ca_matvec_load_w), in registers.
-// (conv1's run end: its share of the mean, SRMI_CA_MPART)
+// (conv1's run end: its share of the mean)
 __device__ __forceinline__ void ca_matvec_load_w(const bf16_t* wimg, int tid, uint2 (&wv)[2][9]) {
   const int co = tid >> 3, pc = tid & 7;  // W2[co][ci][tap] at wimg[(tap * 64 + co) * 64 + ci]
 #pragma unroll

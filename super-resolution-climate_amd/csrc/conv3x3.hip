@@ -439,10 +439,7 @@ int conv3x3_launch(const ConvParams& p, int epi, hipStream_t st) {
         if (!p.cas.w1 || !p.cas.b1 || !p.cas.w2 || !p.cas.b2 || !p.cas.bc2 || !p.cas.rec || p.cas.CR < 4 ||
             p.cas.CR > 32 || p.cas.CR % 4)
           return SRMI_ERR_ARG;
-        // SRMI_CA_MPART: s from conv1's partial means; else from t's border lines
-        if (SRMI_CA_MPART ? (!p.cas.mpart || p.cas.nruns < 1)
-                          : (!p.cas.t || !p.cas.part || p.cas.nstrips != conv3x3_nstrips(p.H, p.W)))
-          return SRMI_ERR_ARG;
+        if (!p.cas.mpart || p.cas.nruns < 1) return SRMI_ERR_ARG;  // (s from conv1's partial means)
       } else if (!p.escale) {
         return SRMI_ERR_ARG;
       }

@@ -66,17 +66,12 @@ struct EpiPre {
 
 // the gradient-stream epilogues (DG_ACC_CA, DG_ACC) add their fp32 operands to the
 // staged dgrad in the 1 KiB run layout of the stores instead of the MFMA layout
-// h' = h + s u into the residual pair: the inference RCAB's conv2 (u never stored) and
-// the training one's (u stored for backward, and rounded to bf16 before the product)
+// h' = h + s u into the residual pair, u rounded to bf16 before the product (staged once as
+// bf16): the inference RCAB's conv2 (u never stored) and the training one's (u stored for
+// backward)
 template <int EPI>
 constexpr bool epi_cr() {
   return EPI == EPI_CA_RESID || EPI == EPI_CA_RESID_U;
-}
-// conv2's h' = h + s u with u rounded to bf16 first (staged once as bf16): the training
-// conv2 always (it stores that u for backward), the inference one per SRMI_INFER_BF16U
-template <int EPI>
-constexpr bool epi_cr_bf16() {
-  return EPI == EPI_CA_RESID_U || (EPI == EPI_CA_RESID && SRMI_INFER_BF16U);
 }
 // the bf16 in-group gradient stream's epilogues (with / without the stream's input r1b)
 template <int EPI>
@@ -160,8 +155,8 @@ __device__ __forceinline__ float relu_mask(uint32_t bits16, float v) {
 // lane's read of another lane's staged data above that lane's write.
 __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }
 
-// conv1's share of its image's CA mean (EPI_RELU_POOL with cas_on, training,
-// SRMI_CA_MPART): what the run's epilogues gather for ca_matvec at the run's end
+// conv1's share of its image's CA mean (EPI_RELU_POOL with cas_on, training): what the
+// run's epilogues gather for ca_matvec at the run's end
 struct CaPart {
   float colA[4][4], colB[4][4];  // [c][r]: the lane's sums of column 0 / column W-1 of t
   float tacc;                    // tid < 64: T over the run's strips, channel tid
@@ -258,7 +253,7 @@ __device__ __forceinline__ void conv_epilogue2(const ConvParams& p, f32x4 (&acc)
           ps1[c][3] += v[3] * bf2f(uu.y >> 16);
         }
       }
-      if constexpr (epi_cr_bf16<EPI>()) {  // u in bf16: the product's operand (and stored for backward)
+      if constexpr (epi_cr<EPI>()) {  // u in bf16: the product's operand (and stored for backward)
         bv[pt][c] = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
         continue;
       }
@@ -307,10 +302,10 @@ __device__ __forceinline__ void conv_epilogue2(const ConvParams& p, f32x4 (&acc)
     }
   }
   const int lane = tid & 63;
-  // conv2 with u rounded to bf16 before anything reads it (epi_cr_bf16): the row is
-  // staged once as bf16 (128 B per pixel, chunk-swizzled: one barrier, not the fp32
-  // path's two halves and four) and read back in the pair's run layout
-  if constexpr (epi_cr_bf16<EPI>()) {
+  // conv2 (epi_cr), u rounded to bf16 before anything reads it: the row is staged once
+  // as bf16 (128 B per pixel, chunk-swizzled, one barrier) and read back in the pair's
+  // run layout
+  if constexpr (epi_cr<EPI>()) {
     constexpr int HALF = NPT * 8, RUNS = HALF / 4;
     static_assert(kShared, "the 8-wave body");
 #pragma unroll
@@ -368,8 +363,6 @@ __device__ __forceinline__ void conv_epilogue2(const ConvParams& p, f32x4 (&acc)
       constexpr int RUNS = HALF / 4;  // 1 KiB runs per half
       const auto rf = wt_rsrc(p.yf, (uint32_t)((size_t)p.N * HW * p.Cout * 4));
       [[maybe_unused]] const auto rbb = wt_rsrc(p.yb, (uint32_t)((size_t)p.N * HW * p.Cout * 2));
-      [[maybe_unused]] const auto rph = wt_rsrc(p.yph, (uint32_t)((size_t)p.N * HW * p.Cout * 2));
-      [[maybe_unused]] const auto rpl = wt_rsrc(p.ypl, (uint32_t)((size_t)p.N * HW * p.Cout));
       const size_t pix0 = (size_t)n * HW + (size_t)y * p.W + x0;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -389,21 +382,6 @@ __device__ __forceinline__ void conv_epilogue2(const ConvParams& p, f32x4 (&acc)
           const int i = kShared ? 2 * j + half_id : j;
           const int lin = i * 1024 + lane * 16, lpx = lin >> 8, c = (lin >> 4) & 15;
           float4 val = *reinterpret_cast<const float4*>(stage + lpx * 256 + ((c ^ (lpx & 15)) << 4));
-          if constexpr (epi_cr<EPI>()) {  // (EPI_CA_RESID with SRMI_INFER_BF16U = 0: fp32 u)
-            // h' = h + s u in the run layout (the lane's channels 4c..4c+3: s in fs), out as the pair
-            const int q = h * (kShared ? RUNS / 2 : RUNS) + j;
-            float4 hh = e.r1[q / NCT][q % NCT];
-            if (p.r1h)
-              hh = pair_decode4(make_uint2(__float_as_uint(hh.x), __float_as_uint(hh.y)), __float_as_uint(hh.z));
-            const uint32_t oe = (uint32_t)((pix0 + h * HALF + lpx) * p.Cout + cb * 64 + c * 4);  // element
-            const float o0 = fmaf(val.x, fs.x, hh.x), o1 = fmaf(val.y, fs.y, hh.y);
-            const float o2 = fmaf(val.z, fs.z, hh.z), o3 = fmaf(val.w, fs.w, hh.w);
-            uint2 hi;
-            const uint32_t lo = pair_encode4(o0, o1, o2, o3, hi);
-            st_wt8(rph, p.yph, oe * 2, hi);
-            st_wt4(rpl, p.ypl, oe, lo);
-            continue;
-          }
           if constexpr (kRun) {
             // g += dx in the run layout; the lane's channels 4c..4c+3 (c = lane & 15)
             // are the same in every run, so its sums accumulate in registers
@@ -572,13 +550,15 @@ __device__ __forceinline__ void conv_epilogue2(const ConvParams& p, f32x4 (&acc)
 
 constexpr int kFragBuf = 2;  // register buffers of A/B fragments (K-steps)
 
+// the epilogues the 8-wave body runs in its deferred form (conv64_body_defer): in training
+// the two dgrads of the fused RCAB backward, in the one-launch inference RCAB conv1's
 template <int EPI>
 constexpr bool conv64_defers() {
-  return ((SRMI_DEFER & 1) && EPI == EPI_RELU_BF16) || ((SRMI_DEFER & 2) && EPI == EPI_POOL_BF16) ||
-         ((SRMI_DEFER & 4) && EPI == EPI_DG_RELUMASK) || ((SRMI_DEFER & 8) && EPI == EPI_DG_ACC_CA) ||
-         ((SRMI_DEFER & 16) && EPI == EPI_RELU_POOL) || ((SRMI_DEFER & 32) && EPI == EPI_CA_RESID) ||
-         ((SRMI_DEFER & (64 | 128)) && EPI == EPI_DG_ACC_CA16);
-  // (EPI_CA_RESID_U: the non-deferred body only)
+#ifdef SRMI_TU_INFER
+  return EPI == EPI_RELU_POOL;
+#else
+  return EPI == EPI_DG_RELUMASK || EPI == EPI_DG_ACC_CA16;
+#endif
 }
 template <int TW, int EPI>
 __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_len, int bid, char* smem, int tail,
@@ -639,11 +619,11 @@ __device__ __forceinline__ void conv64_body(const ConvParams& p, int run_len, in
   // prologue's wait and land under those MFMAs
   [[maybe_unused]] CaScalePre cq;
   constexpr bool kCas = epi_cr<EPI>() && NW == 8;  // (the scale needs 512 threads)
-  // conv1 with cas_on (training, SRMI_CA_MPART): its share of the image's CA mean
+  // conv1 with cas_on (training): its share of the image's CA mean
   constexpr bool kMp = EPI == EPI_RELU_POOL && NW == 8;
-  // conv2 reading those (the training EPI_CA_RESID_U under SRMI_CA_MPART; the launch
-  // refuses cas_on without mpart there) or computing the scale from t (the inference one)
-  constexpr bool kFromMp = EPI == EPI_CA_RESID_U && SRMI_CA_MPART;
+  // conv2 reading those (the training EPI_CA_RESID_U; the launch refuses cas_on without
+  // mpart there) or computing the scale from t (the inference one)
+  constexpr bool kFromMp = EPI == EPI_CA_RESID_U;
   [[maybe_unused]] CaPart cpart;
   [[maybe_unused]] uint2 w2v[2][9];  // the lane's slices of conv2's filter image (run end)
   [[maybe_unused]] const bool cpon = kMp && p.cas_on;
@@ -856,7 +836,7 @@ __device__ __forceinline__ void conv64_body(const ConvParams& p, int run_len, in
     STAMP(sj + 3);
     // LDS-only barrier: this strip's global stores stay in flight into the next strip
     // (the bf16-staged conv2 epilogues run it themselves, after their last stage reads)
-    if constexpr (!epi_cr_bf16<EPI>()) {
+    if constexpr (!epi_cr<EPI>()) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -898,9 +878,10 @@ __device__ __forceinline__ void conv64_body(const ConvParams& p, int run_len, in
 }
 
 // ============================================================================
-// Deferred-epilogue form of the 8-wave body (the four hot epilogues: conv1 RELU and
-// conv2 POOL forward, the ReLU-mask dgrad of conv2 and the gradient-stream dgrad of
-// conv1).  In the form above every strip ends with its epilogue behind a barrier:
+// Deferred-epilogue form of the 8-wave body (conv64_defers: the ReLU-mask dgrad of conv2,
+// the bf16 gradient-stream dgrad of conv1, and the inference conv1's RELU_POOL; the forms
+// measured and rejected for the other epilogues are in DESIGN.md section 3).
+// In the form above every strip ends with its epilogue behind a barrier:
 // the MFMA pipe idles for ~2.6 K cycles per strip (bias / mask, packing, LDS
 // staging, two more barriers, the stores) against ~3.5 K cycles of MFMA
 // (profiles/r02_conv_stamps_8wave.txt).  Here the epilogue of strip k-1 runs
@@ -908,19 +889,19 @@ __device__ __forceinline__ void conv64_body(const ConvParams& p, int run_len, in
 // the previous strip's accumulators held in registers; its operands (ReLU output t,
 // gradient stream g, CA input u) are loaded at the first K-steps of strip k; strip
 // k ends with ONE barrier (ring-slot release + group k+2's DMA published).  Only
-// the last strip of a run keeps an exposed epilogue.
+// the last strip of a run keeps an exposed epilogue.  DG_ACC_CA16 (kG16) instead runs
+// its epilogue right after its own strip's K-loop, its operands loaded at that strip's
+// first K-steps: still no LDS staging and one barrier per strip.
 //
-// No LDS staging: each wave stores its own results straight from registers.  For
-// the bf16 outputs the filter rows are read permuted -- accumulator row 4fk + r of
-// tile c is output channel ct0*16 + 8fk + 4c + r -- so a lane holds 8 contiguous
-// channels of its pixel and one 16-byte store per pixel tile writes, per pixel, the
-// wave's whole 64-byte channel half (16 such runs per instruction).  The fp32
-// gradient stream keeps the natural rows: a lane's 4 channels of a tile are 16
-// contiguous bytes, 64 contiguous bytes per pixel per store.  Channel sums (POOL,
-// DG_ACC_CA) go through two LDS buffers: strip k-1's per-row sums are written
-// during strip k, summed over the 4 rows and stored during strip k+1.  Results are
-// bit-identical to the form above (same MFMA order per output element, same sum
-// order).
+// No LDS staging: each wave stores its own results straight from registers.  The
+// filter rows are read permuted -- accumulator row 4fk + r of tile c is output
+// channel ct0*16 + 8fk + 4c + r -- so a lane holds 8 contiguous channels of its pixel
+// and one 16-byte store per pixel tile writes, per pixel, the wave's whole 64-byte
+// channel half (16 such runs per instruction).  Channel sums (RELU_POOL, DG_ACC_CA16)
+// go through two LDS buffers: strip k-1's per-row sums are written during strip k,
+// summed over the 4 rows and stored during strip k+1 (kG16: strip k's during strip k,
+// stored during strip k+1).  Results are bit-identical to the form above (same MFMA
+// order per output element, same sum order).
 
 // opaque to the IR passes (a value "redefined" here cannot be computed with earlier)
 __device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
@@ -930,7 +911,6 @@ __device__ __forceinline__ void pin4(f32x4& v) {
   pin(a); pin(b); pin(c); pin(d);
   v = f32x4{a, b, c, d};
 }
-__device__ __forceinline__ void pin4f(float4& v) { pin(v.x); pin(v.y); pin(v.z); pin(v.w); }
 __device__ __forceinline__ void pin4u(uint4& v) { pin(v.x); pin(v.y); pin(v.z); pin(v.w); }
 
 // deferred epilogue stores: write-through (sc1) like the others (SRMI_WT)
@@ -941,10 +921,8 @@ __device__ __forceinline__ void st_defer(__amdgpu_buffer_rsrc_t r, void* base, u
 
 template <int NPT>
 struct DeferOps {
-  uint4 t[NPT];      // DG_RELUMASK: the ReLU output t, 8 bf16 (permuted rows)
-  float4 g[NPT][2];  // DG_ACC_CA: gradient stream in (natural rows)
-  uint2 u[NPT][2];   // DG_ACC_CA: the CA input u
-  uint4 uq[NPT];     // DG_ACC_CA16: the CA input u, 8 bf16 (permuted rows; the stream g in t)
+  uint4 t[NPT];   // DG_RELUMASK: the ReLU output t, 8 bf16 (permuted rows)
+  uint4 uq[NPT];  // DG_ACC_CA16: the CA input u, 8 bf16 (permuted rows; the stream g in t)
 };
 
 template <int TW, int EPI>
@@ -953,16 +931,12 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
   constexpr int NW = 8, NCT = 2;
   using S = Conv2Smem<TW>;
   constexpr int NPT = TW / 16;
-  constexpr bool kPerm = EPI != EPI_DG_ACC_CA;  // bf16 output: permuted filter rows
-  constexpr bool kG16 = EPI == EPI_DG_ACC_CA16;  // the bf16 gradient stream: g in / out as 8 bf16 per lane
-  constexpr bool kPart = EPI == EPI_POOL_BF16 || EPI == EPI_DG_ACC_CA || EPI == EPI_RELU_POOL || kG16;
-  constexpr bool kCA = EPI == EPI_DG_ACC_CA;
-  constexpr bool kS1 = kCA || kG16;  // the second channel sum (g * u)
-  // DG_ACC_CA16 with SRMI_DEFER bit 128: this body's register-direct epilogue, run right
-  // after its own strip's K-loop (operands loaded at the strip's first K-steps) instead of
-  // inside the next strip's: no LDS staging, one barrier per strip
-  constexpr bool kImm = kG16 && (SRMI_DEFER & 128);
-  constexpr bool kCR = EPI == EPI_CA_RESID;  // h' = h + s u: 8 contiguous channels per lane (permuted rows)
+  static_assert(EPI == EPI_DG_RELUMASK || EPI == EPI_DG_ACC_CA16 || EPI == EPI_RELU_POOL, "conv64_defers");
+  // the bf16 gradient stream: g in / out as 8 bf16 per lane, with the second channel sum
+  // (g * u); its register-direct epilogue runs right after its own strip's K-loop (operands
+  // loaded at the strip's first K-steps) instead of inside the next strip's
+  constexpr bool kG16 = EPI == EPI_DG_ACC_CA16;
+  constexpr bool kPart = EPI == EPI_RELU_POOL || kG16;  // channel sums
   constexpr int ES = 10;  // K-step of the first deferred epilogue tile
   char* wl = smem;
   char* ring = smem + S::WB;
@@ -1050,7 +1024,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
   };
 
   // channel of accumulator row (c, r) of this lane, and the lane's channel bases
-  auto chan = [&](int c, int rr) -> int { return kPerm ? ct0 * 16 + 8 * fk + 4 * c + rr : (ct0 + c) * 16 + 4 * fk + rr; };
+  auto chan = [&](int c, int rr) -> int { return ct0 * 16 + 8 * fk + 4 * c + rr; };
   float4 bias[NCT];
   {
     const float* bp = p.bias ? p.bias : reinterpret_cast<const float*>(kZeros);
@@ -1060,9 +1034,9 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
   {
     const uint32_t wbase = lds_u32(wl);
     // the filter image uses the swz128t chunk swizzle (c ^ (bit1, bit3 of the row)):
-    // conflict-free for the permuted A rows (8 (fr >> 2) + 4c + (fr & 3)) as well as
-    // the natural ones, where swz128 would collide 2-way on the permuted rows and make
-    // the K-loop LDS-bound (20 -> 28 LDS cycles per wave and K-step against 24 of MFMA)
+    // conflict-free for the permuted A rows (8 (fr >> 2) + 4c + (fr & 3)), where swz128
+    // would collide 2-way and make the K-loop LDS-bound (20 -> 28 LDS cycles per wave and
+    // K-step against 24 of MFMA)
     for (int i = wv_s; i < 72; i += NW) {
       const int tap = i >> 3, rw = 8 * (i & 7) + (lane >> 3);
       const int c = (lane & 7) ^ ((((rw >> 1) & 1) << 1) | (((rw >> 3) & 1) << 2));
@@ -1108,33 +1082,24 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
   }
   STAMP(1);
   // A-fragment rows: lane fr of tile c reads the filter row of the channel its
-  // accumulator row fr will hold (permuted for bf16 outputs)
+  // accumulator row fr will hold (permuted)
   uint32_t aoff[2][NCT];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
     for (int c = 0; c < NCT; ++c) {
-      const int arow = kPerm ? ct0 * 16 + 8 * (fr >> 2) + 4 * c + (fr & 3) : (ct0 + c) * 16 + fr;
+      const int arow = ct0 * 16 + 8 * (fr >> 2) + 4 * c + (fr & 3);
       aoff[kk][c] = swz128t(arow, kk * 4 + fk);
     }
   __syncthreads();
 
-  const auto rout = kPerm ? wt_rsrc(p.yb, (uint32_t)((size_t)p.N * HW * p.Cout * 2))
-                          : wt_rsrc(p.yf, (uint32_t)((size_t)p.N * HW * p.Cout * 4));
-  [[maybe_unused]] const auto rph = wt_rsrc(p.yph, (uint32_t)((size_t)p.N * HW * p.Cout * 2));
-  [[maybe_unused]] const auto rpl = wt_rsrc(p.ypl, (uint32_t)((size_t)p.N * HW * p.Cout));
-  [[maybe_unused]] float sv[8];  // CA_RESID: s of the lane's 8 channels
-  if constexpr (kCR) {
-    const float* sp = p.escale + (size_t)n * p.escale_stride + ct0 * 16 + 8 * fk;
-    const float4 a = *reinterpret_cast<const float4*>(sp), b = *reinterpret_cast<const float4*>(sp + 4);
-    sv[0] = a.x; sv[1] = a.y; sv[2] = a.z; sv[3] = a.w; sv[4] = b.x; sv[5] = b.y; sv[6] = b.z; sv[7] = b.w;
-  }
+  const auto rout = wt_rsrc(p.yb, (uint32_t)((size_t)p.N * HW * p.Cout * 2));
   const int nstrips_all = nsy * nsx;
   f32x4 accp[NPT][NCT];  // the previous strip's accumulators
   DeferOps<NPT> ops;     // operands of the pending epilogue
 
   // operand loads of the epilogue of strip kp (pixel row 4 kp + row), load slot i
-  constexpr int NLD = (EPI == EPI_DG_RELUMASK || kCR) ? NPT : ((kCA || kG16) ? NPT * 2 : 0);
+  constexpr int NLD = EPI == EPI_DG_RELUMASK ? NPT : (kG16 ? NPT * 2 : 0);
   auto op_load = [&](int kp, int i) __attribute__((always_inline)) {
     const int yy = 4 * kp + row;
     if constexpr (EPI == EPI_DG_RELUMASK) {
@@ -1146,22 +1111,6 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
       const size_t o = pix * p.Cout + cb * 64 + chan(0, 0);
       if (i & 1) ops.uq[pt] = *reinterpret_cast<const uint4*>(p.aux + o);
       else ops.t[pt] = *reinterpret_cast<const uint4*>(p.r1b + o);
-    } else if constexpr (kCA) {
-      const int pt = i / NCT, c = i % NCT;
-      const size_t pix = (size_t)n * HW + (size_t)yy * p.W + x0 + pt * 16 + fr;
-      const size_t o = pix * p.Cout + cb * 64 + chan(c, 0);
-      ops.g[pt][c] = *reinterpret_cast<const float4*>(p.r1 + o);
-      ops.u[pt][c] = *reinterpret_cast<const uint2*>(p.aux + o);
-    } else if constexpr (kCR) {  // h: the pair (hi 16 B + lo 8 B) or fp32 (32 B), 8 channels
-      const size_t pix = (size_t)n * HW + (size_t)yy * p.W + x0 + i * 16 + fr;
-      const size_t o = pix * p.Cout + cb * 64 + chan(0, 0);
-      if (p.r1h) {
-        ops.t[i] = *reinterpret_cast<const uint4*>(p.r1h + o);
-        ops.u[i][0] = *reinterpret_cast<const uint2*>(p.r1l + o);
-      } else {
-        ops.g[i][0] = *reinterpret_cast<const float4*>(p.r1 + o);
-        ops.g[i][1] = *reinterpret_cast<const float4*>(p.r1 + o + 4);
-      }
     }
   };
   // epilogue of pixel tile pt of strip kp from accp
@@ -1176,52 +1125,9 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
       pin4u(ops.t[pt]);
       pin4u(ops.uq[pt]);
     }
-    if constexpr (kCR) {
-      if (p.r1h) {
-        pin4u(ops.t[pt]);
-        pin(ops.u[pt][0].x);
-        pin(ops.u[pt][0].y);
-      } else {
-        pin4f(ops.g[pt][0]);
-        pin4f(ops.g[pt][1]);
-      }
-    }
-    if constexpr (kCA) {
-#pragma unroll
-      for (int c = 0; c < NCT; ++c) {
-        pin4f(ops.g[pt][c]);
-        pin(ops.u[pt][c].x);
-        pin(ops.u[pt][c].y);
-      }
-    }
     const int yy = 4 * kp + row;
     const size_t pix = (size_t)n * HW + (size_t)yy * p.W + x0 + pt * 16 + fr;
-    if constexpr (kCR) {
-      float hv[8];
-      if (p.r1h) {
-        const uint4 th = ops.t[pt];
-        const uint2 tl = ops.u[pt][0];
-        const float4 a = pair_decode4(make_uint2(th.x, th.y), tl.x), b = pair_decode4(make_uint2(th.z, th.w), tl.y);
-        hv[0] = a.x; hv[1] = a.y; hv[2] = a.z; hv[3] = a.w; hv[4] = b.x; hv[5] = b.y; hv[6] = b.z; hv[7] = b.w;
-      } else {
-        const float4 a = ops.g[pt][0], b = ops.g[pt][1];
-        hv[0] = a.x; hv[1] = a.y; hv[2] = a.z; hv[3] = a.w; hv[4] = b.x; hv[5] = b.y; hv[6] = b.z; hv[7] = b.w;
-      }
-      float o[8];
-#pragma unroll
-      for (int c = 0; c < NCT; ++c) {
-        const f32x4 v = accp[pt][c];
-        const float b[4] = {bias[c].x, bias[c].y, bias[c].z, bias[c].w};
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) o[4 * c + rr] = fmaf(v[rr] + b[rr], sv[4 * c + rr], hv[4 * c + rr]);
-      }
-      uint2 h0, h1;
-      const uint32_t l0 = pair_encode4(o[0], o[1], o[2], o[3], h0);
-      const uint32_t l1 = pair_encode4(o[4], o[5], o[6], o[7], h1);
-      const uint32_t oe = (uint32_t)(pix * p.Cout + cb * 64 + chan(0, 0));
-      st_wt16(rph, p.yph, oe * 2, make_uint4(h0.x, h0.y, h1.x, h1.y));
-      st_wt8(rpl, p.ypl, oe, make_uint2(l0, l1));
-    } else if constexpr (kG16) {
+    if constexpr (kG16) {
       // g = bf16(acc + g_in): the CA sums take the rounded (stored) value, as conv_epilogue2
       const uint32_t gw[4] = {ops.t[pt].x, ops.t[pt].y, ops.t[pt].z, ops.t[pt].w};
       const uint32_t uw[4] = {ops.uq[pt].x, ops.uq[pt].y, ops.uq[pt].z, ops.uq[pt].w};
@@ -1239,7 +1145,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
         ps1[c][r0 + 1] += rb * bf2f(uw[q] >> 16);
       }
       st_defer(rout, p.yb, (uint32_t)((pix * p.Cout + cb * 64 + chan(0, 0)) * 2), make_uint4(ow[0], ow[1], ow[2], ow[3]));
-    } else if constexpr (kPerm) {
+    } else {
       float o[8];
 #pragma unroll
       for (int c = 0; c < NCT; ++c) {
@@ -1248,12 +1154,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           float x = v[rr];
-          if constexpr (EPI == EPI_RELU_BF16) x = fmaxf(x + b[rr], 0.f);
           if constexpr (EPI == EPI_RELU_POOL) x = fmaxf(x + b[rr], 0.f);  // (summed as bf16 below)
-          if constexpr (EPI == EPI_POOL_BF16) {
-            x += b[rr];
-            ps0[c][rr] += x;
-          }
           if constexpr (EPI == EPI_DG_RELUMASK) {
             const uint32_t w = (c ? (rr < 2 ? ops.t[pt].z : ops.t[pt].w) : (rr < 2 ? ops.t[pt].x : ops.t[pt].y));
             x = p.alpha * relu_mask((rr & 1) ? (w >> 16) : (w & 0xFFFFu), x);
@@ -1268,20 +1169,6 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
         for (int i = 0; i < 8; ++i) ps0[i >> 2][i & 3] += bf2f((i & 1) ? (w[i >> 1] >> 16) : (w[i >> 1] & 0xFFFFu));
       }
       st_defer(rout, p.yb, (uint32_t)((pix * p.Cout + cb * 64 + chan(0, 0)) * 2), val);
-    } else {
-#pragma unroll
-      for (int c = 0; c < NCT; ++c) {
-        const f32x4 a = accp[pt][c];
-        const float4 gg = ops.g[pt][c];
-        const uint2 uu = ops.u[pt][c];
-        const float v[4] = {a[0] + gg.x, a[1] + gg.y, a[2] + gg.z, a[3] + gg.w};
-        st_defer(rout, p.yf, (uint32_t)((pix * p.Cout + cb * 64 + chan(c, 0)) * 4), make_float4(v[0], v[1], v[2], v[3]));
-        ps0[c][0] += v[0]; ps0[c][1] += v[1]; ps0[c][2] += v[2]; ps0[c][3] += v[3];
-        ps1[c][0] += v[0] * bf2f(uu.x & 0xFFFFu);
-        ps1[c][1] += v[1] * bf2f(uu.x >> 16);
-        ps1[c][2] += v[2] * bf2f(uu.y & 0xFFFFu);
-        ps1[c][3] += v[3] * bf2f(uu.y >> 16);
-      }
     }
   };
   // this wave's row sums of strip kp -> red buffer kp & 1
@@ -1293,10 +1180,10 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
       for (int rr = 0; rr < 4; ++rr) {
         const float s0 = sum16(ps0[c][rr]);
         float s1 = 0.f;
-        if constexpr (kS1) s1 = sum16(ps1[c][rr]);
+        if constexpr (kG16) s1 = sum16(ps1[c][rr]);
         if (fr == 0) {
           rb[(row * 2 + 0) * 64 + chan(c, rr)] = s0;
-          if constexpr (kS1) rb[(row * 2 + 1) * 64 + chan(c, rr)] = s1;
+          if constexpr (kG16) rb[(row * 2 + 1) * 64 + chan(c, rr)] = s1;
         }
       }
   };
@@ -1306,7 +1193,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
     const size_t rec = ((size_t)n * nstrips_all + kp * nsx + sx) * p.part_stride;
     if (tid < 64) {
       p.part[rec + cb * 64 + tid] = rb[tid] + rb[128 + tid] + rb[256 + tid] + rb[384 + tid];
-    } else if (kS1 && tid < 128) {
+    } else if (kG16 && tid < 128) {
       const int c = tid - 64;
       p.part[rec + 64 + c] = rb[64 + c] + rb[192 + c] + rb[320 + c] + rb[448 + c];
     }
@@ -1325,7 +1212,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
     constexpr bool LAST = decltype(last_tag)::value;
     const int y = 4 * k + row;
     const bool pf = (k + 1 < k1);
-    const bool red_store = kPart && (k - (kImm ? 1 : 2) >= k0) && tid < (kS1 ? 128 : 64);
+    const bool red_store = kPart && (k - (kG16 ? 1 : 2) >= k0) && tid < (kG16 ? 128 : 64);
     [[maybe_unused]] const int sj = 2 + 5 * min(k - k0, 11);
     STAMP(sj);
     uint32_t boff[3][3][2];
@@ -1362,11 +1249,11 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
       // 0-2), group k+2's DMA (0-3), the deferred stores (K-steps ES..), the
       // previous-but-one strip's partial record (17): the DMA is waited for at the
       // end with a count of the stores behind it
-      if constexpr ((PREV || kImm) && NLD > 0) {
+      if constexpr ((PREV || kG16) && NLD > 0) {
         constexpr int PER = (NLD + 2) / 3;
 #pragma unroll
         for (int i = 0; i < PER; ++i)
-          if (st < 3 && st * PER + i < NLD) op_load(kImm ? k : k - 1, st * PER + i);
+          if (st < 3 && st * PER + i < NLD) op_load(kG16 ? k : k - 1, st * PER + i);
       }
       if (st < NGW && pf && wv_s + NW * st < NGRP) group_dma_one(k + 2, st);
       __builtin_amdgcn_sched_barrier(0);
@@ -1391,34 +1278,20 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
           if (st == ES + NPT) part_rows(k - 1);
       }
       if constexpr (kPart)
-        if (st == 17 && red_store) part_store(kImm ? k - 1 : k - 2);
+        if (st == 17 && red_store) part_store(kG16 ? k - 1 : k - 2);
       if constexpr (EPI == EPI_DG_RELUMASK) {
-        // du of group k+2 (gx), one DMA piece per K-step behind that step's MFMAs over the
-        // strip's last K-steps, each piece read one K-step ahead: the pieces (issued at
-        // K-steps 0-3) have landed once only the deferred stores of K-steps ES.. may still
-        // be in flight behind them
-        constexpr int GXS = 18 - NGW;
-        if (SRMI_GX_INLOOP == 2 && gx && pf && st >= 17 - 2 * NGW) {
-          // (variant: a piece every other K-step from K-step 18 - 2 NGW, each read the step
-          //  before; the wait at 17 - 2 NGW also takes the deferred epilogue's operands)
-          constexpr int G0 = 17 - 2 * NGW;
+        // du of group k+2 (gx), behind the MFMAs of the strip's last K-steps: one DMA piece
+        // every other K-step from K-step 18 - 2 NGW, each read the step before; the wait at
+        // 17 - 2 NGW (the pieces were issued at K-steps 0-3) also takes the deferred
+        // epilogue's operands
+        constexpr int G0 = 17 - 2 * NGW;
+        if (gx && pf && st >= G0) {
           const int m = (st - G0) >> 1;
           if (st == G0) wait_vm<0>();
           if (((st - G0) & 1) == 0) {
             if (gx_ok(k + 2, m)) gxv[m < NGW ? m : 0] = *gx_ptr(k + 2, m);
           } else if (gx_ok(k + 2, m)) {
             *gx_ptr(k + 2, m) = du_from_g8(gxv[m < NGW ? m : 0], gxs, gxm);
-          }
-        }
-        if (SRMI_GX_INLOOP == 1 && gx && pf && st >= GXS - 1) {
-          if (st == GXS - 1) {
-            if constexpr (PREV) wait_vm<NPT>();
-            else wait_vm<0>();
-            if (gx_ok(k + 2, 0)) gxv[0] = *gx_ptr(k + 2, 0);
-          } else {
-            const int m = st - GXS;
-            if (m + 1 < NGW && gx_ok(k + 2, m + 1)) gxv[m + 1 < NGW ? m + 1 : 0] = *gx_ptr(k + 2, m + 1);
-            if (gx_ok(k + 2, m)) *gx_ptr(k + 2, m) = du_from_g8(gxv[m], gxs, gxm);
           }
         }
       }
@@ -1434,8 +1307,8 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
     STAMP(sj + 1);
     // group k+2 has landed once only this strip's deferred stores (and the partial
     // record) may still be in flight behind it
-    constexpr int NST = PREV ? (kCR ? 2 * NPT : (kPerm ? NPT : NPT * NCT)) : 0;
-    if constexpr (kImm) {
+    constexpr int NST = PREV ? NPT : 0;
+    if constexpr (kG16) {
       // the strip's own epilogue: its operands, group k+2 and the partial record landed
       wait_vm<0>();
 #pragma unroll
@@ -1453,9 +1326,6 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
       wait_vm<NST + 1>();
     } else {
       wait_vm<NST>();
-    }
-    if constexpr (EPI == EPI_DG_RELUMASK && !SRMI_GX_INLOOP) {
-      if (gx && pf) gx_group(k + 2);  // (its pieces landed: the wait above)
     }
     STAMP(sj + 2);
 #ifdef SRMI_STAMPS
@@ -1476,7 +1346,7 @@ __device__ __forceinline__ void conv64_body_defer(const ConvParams& p, int run_l
   };
   using T = std::true_type;
   using F = std::false_type;
-  if constexpr (kImm) {
+  if constexpr (kG16) {
 #pragma unroll 1
     for (int k = k0; k < k1; ++k) strip(k, F{}, F{});
     part_store(k1 - 1);  // (its rows' sums published by the last strip's barrier)

@@ -196,7 +196,7 @@ struct srmi_engine {
   bf16_t* PS[3];  // pixel-shuffle outputs (scale s: [N][h*2^k][w*2^k][64])
   float *rec, *brec;
   float *ppool, *pacc;
-  float* mpart;  // conv1's partial CA means [N][runs per image <= nstrips][64] (SRMI_CA_MPART)
+  float* mpart;  // conv1's partial CA means [N][runs per image <= nstrips][64]
   // backward
   float *GAf, *GBf, *dRESf;
   bf16_t *GAb, *GBb, *DU, *DZ, *dRESb;
@@ -208,16 +208,8 @@ struct srmi_engine {
   // per launch, so the reductions can wait for the group's end (one launch for all)
   std::vector<float*> slab_sets, bslab_sets;
   size_t slab_r_floats = 0, bslab_r_floats = 0;
-  // (SRMI_F2_MLP 0: the reductions ride in the next launch pair's CA-backward launch, so two
-  //  sets per conv alternate -- RCAB b by the parity of b, the group tail the other parity of
-  //  RCAB nblocks' -- and only four sets are ever touched)
-  int slab_idx(int b, int c) const {
-    if (SRMI_F2_MLP) return b * 2 + c;
-    const int q = b == 0 ? ((P.cfg.nblocks & 1) ^ 1) : (b & 1);
-    return (q + 1) * 2 + c;  // (sets 2 .. 5: the group tail's own (0, 1) slot is never allocated)
-  }
-  float* slab_r(int b, int c) const { return slab_sets[slab_idx(b, c)]; }
-  float* bslab_r(int b, int c) const { return bslab_sets[slab_idx(b, c)]; }
+  float* slab_r(int b, int c) const { return slab_sets[b * 2 + c]; }
+  float* bslab_r(int b, int c) const { return bslab_sets[b * 2 + c]; }
   float* lpart;
   int lpart_n;
   float* zeros;  // 256 zero bytes (DMA padding source)
@@ -258,12 +250,6 @@ struct srmi_engine {
   }
   float* brecp(int g, int b) const { return brec + (size_t)(g * P.cfg.nblocks + (b - 1)) * N * 224; }
 };
-
-// bf16 partial slabs for the RCAB filter gradients (tuning.hpp).  The other filter
-// gradients (group / body tails, upsamplers: 26 launches per step) keep fp32 slabs:
-// bf16 there measured +0.3 % (noise) and doubled the split dependence of their sums
-// (one engine of 16 tiles vs 2 x 2 engines of 4: 2.4e-4 rel-L2 of the gradient)
-constexpr bool kSlab16 = SRMI_SLAB16 != 0;
 
 // The RCAB filter gradients run beside their dgrad convs (one fused launch, the
 // CU budget split in halves), so their row chunks are sized for HALF the engine's
@@ -352,7 +338,7 @@ static size_t carve(srmi_engine* e, char* base) {
                               (e->w % 48 == 0 ? e->w / 48 : 1));
       e->slab_r_floats = ns * 64 * 576;
       e->bslab_r_floats = ns * 64;
-      const int nsets = SRMI_F2_MLP ? (P.cfg.nblocks + 1) * 2 : 6;  // (slab_idx)
+      const int nsets = (P.cfg.nblocks + 1) * 2;  // (slab_r)
       e->slab_sets.assign(nsets, nullptr);
       e->bslab_sets.assign(nsets, nullptr);
       for (int i = 0; i < nsets; ++i) {
@@ -505,7 +491,10 @@ static int conv_dgrad(srmi_engine* e, const ConvRef& c, const bf16_t* dy, int n,
 }
 
 // filter gradient of conv c into `slab`/`bslab` (capacity cap/bcap floats); the
-// reduction into grads is returned in *red
+// reduction into grads is returned in *red.  slab16: bf16 partial slabs, the RCAB filter
+// gradients'.  The other filter gradients (group / body tails, upsamplers: 26 launches per
+// step) keep fp32 slabs: bf16 there measured +0.3 % (noise) and doubled the split dependence
+// of their sums (one engine of 16 tiles vs 2 x 2 engines of 4: 2.4e-4 rel-L2 of the gradient)
 static int wgrad_params(srmi_engine* e, const ConvRef& c, const bf16_t* x, const bf16_t* dy, int n, int H, int W,
                         float* grads, bool with_bias, float alpha, int row_splits, float* slab, float* bslab,
                         size_t cap, size_t bcap, WgradParams* out, ReduceSet* red, bool slab16 = false) {
@@ -731,16 +720,14 @@ static bool use_rcab_infer(const srmi_engine* e) {
 // (EPI_RELU_POOL); conv2 (EPI_CA_RESID_U) stores u for backward and adds s bf16(u) into
 // the residual pair in its epilogue, with s = the CA MLP of mean(u), and mean(u) from t's
 // statistics and conv2's bf16 filter image (ca_scale.hpp), computed by every conv2
-// workgroup in its prologue (1; its own launch between the convs measured -2.5 %).
-// 0: conv1, conv2 + pool writing u, the CA pass (ca_fwd) -- the exact-fp32 mode and tiles
+// workgroup in its prologue (its own launch between the convs measured -2.5 %).
+// false: conv1, conv2 + pool writing u, the CA pass (ca_fwd) -- the exact-fp32 mode and tiles
 // other than 48 wide always run this form; SRMI_FLAG_CA_PASS selects it at run time.
-// bf16, 48-wide tiles, a bottleneck the scale code handles.
-static int ca_fwd_mode(const srmi_engine* e) {
+// true: bf16, 48-wide tiles, a bottleneck the scale code handles.
+static bool ca_fwd_mode(const srmi_engine* e) {
   const int CR = 64 / e->P.cfg.reduction;
-  if (!e->train || e->f32 || e->P.cfg.arch != SRMI_ARCH_RCAN || e->w != 48 || e->h % 4 || CR < 4 || CR > 32 ||
-      CR % 4 || (e->P.cfg.flags & SRMI_FLAG_CA_PASS))
-    return 0;
-  return SRMI_CA_FWD;
+  return e->train && !e->f32 && e->P.cfg.arch == SRMI_ARCH_RCAN && e->w == 48 && e->h % 4 == 0 && CR >= 4 &&
+         CR <= 32 && CR % 4 == 0 && !(e->P.cfg.flags & SRMI_FLAG_CA_PASS);
 }
 
 // ------------------------------------------------------------------ forward
@@ -771,15 +758,13 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
           ConvParams c1 = fwd_params(e, r.c1, e->hb(g, b - 1), n, h, w, e->Tm(g, b), nullptr, nullptr, e->ppool, 1.f);
           ConvParams c2 = fwd_params(e, r.c2, e->Tm(g, b), n, h, w, e->Um(g, b), nullptr, b == 1 ? rin : nullptr,
                                      nullptr, 1.f);
-          // SRMI_CA_MPART: conv1's workgroups leave their share of the CA mean (the matvec
-          // on conv2's bf16 filter image) for conv2, which then reads no t border lines
-          const int nruns = SRMI_CA_MPART ? conv64_runs_per_image(c1) : 0;
-          if (SRMI_CA_MPART) {
-            c1.cas.mpart = e->mpart;
-            c1.cas.nruns = nruns;
-            c1.cas.wimg = c2.w;
-            c1.cas_on = 1;
-          }
+          // conv1's workgroups leave their share of the CA mean (the matvec on conv2's bf16
+          // filter image) for conv2, which then reads no t border lines
+          const int nruns = conv64_runs_per_image(c1);
+          c1.cas.mpart = e->mpart;
+          c1.cas.nruns = nruns;
+          c1.cas.wimg = c2.w;
+          c1.cas_on = 1;
           RC(conv3x3_launch(c1, EPI_RELU_POOL, st));
           if (e->ftrace) RC(ftrace_copy(e, SRMI_FTRACE_PPOOL, g, b, e->ppool, n, st));
           c2.r1h = b == 1 ? nullptr : e->hb(g, b - 1);
@@ -789,10 +774,8 @@ static int forward_impl(srmi_engine* e, const float* prm, const float* lr, float
           const CaScale cas{e->Tm(g, b), e->ppool, nstrips, prm + r.ca_w1, prm + r.ca_b1, prm + r.ca_w2,
                             prm + r.ca_b2, e->pbias + r.c2.pb_off, 64 / R, e->recp(g, b)};
           c2.cas = cas;
-          if (SRMI_CA_MPART) {
-            c2.cas.mpart = e->mpart;
-            c2.cas.nruns = nruns;
-          }
+          c2.cas.mpart = e->mpart;
+          c2.cas.nruns = nruns;
           c2.cas_on = 1;
           RC(conv3x3_launch(c2, EPI_CA_RESID_U, st));
           if (e->ftrace) RC(ftrace_rcab(e, g, b, false, n, st));
@@ -859,7 +842,7 @@ static int backward_stages(const srmi_engine* e) { return e->P.cfg.arch == SRMI_
 // of 4 (the MLP's thread mapping).  Else the CA backward is a launch of its own.
 static bool du_in_f2(const srmi_engine* e, const ConvParams& cp, const WgradParams& wp, int epi) {
   const int CR = 64 / e->P.cfg.reduction;
-  return !e->f32 && !(e->P.cfg.flags & SRMI_FLAG_DU_PASS) && rcab_bwd_du_from_g() && epi == EPI_DG_RELUMASK &&
+  return !e->f32 && !(e->P.cfg.flags & SRMI_FLAG_DU_PASS) && epi == EPI_DG_RELUMASK &&
          rcab_bwd_fusable(cp, wp) && CR % 4 == 0 && CR >= 4 && CR <= 32;
 }
 
@@ -936,17 +919,8 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
       // (srmi_engine_trace: the in-group stream in the engine's operand type)
       const void* gstream = g16 ? static_cast<const void*>(ghb) : ghf;
       if (e->trace) RC(trace_copy(e, SRMI_TRACE_GRB, g, 0, gRb, n, st));
-      // the filter-gradient reductions: collected for one launch at the group's end (or, with
-      // the CA backward's MLP as a launch of its own (SRMI_F2_MLP 0), riding in that launch)
-      ReduceSet prev2{}, prev1{};
-      bool have_prev = false;
+      // the filter-gradient reductions: collected for one launch at the group's end
       std::vector<ReduceSet> group_sets;
-      auto defer_prev = [&]() {
-        if (!have_prev) return;
-        if (prev2.gw || prev2.gb) group_sets.push_back(prev2);
-        if (prev1.gw || prev1.gb) group_sets.push_back(prev1);
-        have_prev = false;
-      };
       // group tail: its dgrad (the bf16 stream's start, with the CA sums of RCAB nb) and its
       // filter gradient as one fused launch, like the RCABs' (slab set (0, 0), reduced with the
       // RCABs'), else (exact fp32, unfusable shapes) the two launches and the reduction in turn
@@ -955,14 +929,13 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
         const ConvParams cp = dgrad_params(e, gt, gRb, n, h, w, &epi, g16 ? ghb : nullptr, g16 ? nullptr : ghf,
                                            nullptr, nullptr, nullptr, e->Um(g, nb), e->pacc, 1.f);
         WgradParams wp{};
+        ReduceSet red{};
         if (g16)
           RC(wgrad_params(e, gt, e->hb(g, nb), gRb, n, h, w, grads, true, 1.f, rs1, e->slab_r(0, 0),
-                          e->bslab_r(0, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &prev2));
+                          e->bslab_r(0, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red));
         if (g16 && rcab_bwd_fusable(cp, wp)) {
           RC(dgrad_with_wgrad(e, cp, epi, wp, 1, st));
-          prev1 = ReduceSet{};  // (no second reduction: gw = gb = null)
-          prev1.Cout = prev2.Cout;
-          have_prev = true;
+          group_sets.push_back(red);
         } else {
           RC(conv_wgrad(e, gt, e->hb(g, nb), gRb, n, h, w, grads, true, 1.f, st));
           RC(conv3x3_launch(cp, epi, st));
@@ -982,7 +955,7 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
         ConvParams cp = dgrad_params(e, r.c2, du, n, h, w, &epi, dz, nullptr, nullptr, nullptr, nullptr, e->Tm(g, b),
                                      nullptr, 1.f);
         RC(wgrad_params(e, r.c2, e->Tm(g, b), du, n, h, w, grads, false, 1.f, rs2, e->slab_r(b, 0), e->bslab_r(b, 0),
-                        e->slab_r_floats, e->bslab_r_floats, &wp, &red2, kSlab16));
+                        e->slab_r_floats, e->bslab_r_floats, &wp, &red2, true));
         // The CALayer backward inside the fused conv2 backward (both its roles run the
         // image's MLP in their prologue and form du = bf16(g s + dm / HW) from the bf16
         // stream on their input rings; ca_bwd.hpp), or as a launch of its own writing du
@@ -991,25 +964,10 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
         if (du_fused) {
           cp.x = wp.dy = ghb;
           cp.gx = wp.gx = CaBwdIn{e->pacc, nstrips, e->recp(g, b), prm + r.ca_w1, prm + r.ca_w2, 64 / R,
-                                  e->brecp(g, b), n, 1.f / (float)HW, SRMI_F2_MLP};
-          if (SRMI_F2_MLP) {
-            defer_prev();
-          } else {  // the MLP launch (brec, dm), the previous pair's reductions riding in it
-            RC(ca_bwd_du_launch(ghb, 1, e->pacc, nstrips, e->recp(g, b), prm + r.ca_w1, prm + r.ca_w2, n, HW, 64, R,
-                                nullptr, e->brecp(g, b), 0, st, have_prev ? &prev2 : nullptr,
-                                have_prev ? &prev1 : nullptr));
-            have_prev = false;
-          }
-        } else if (SRMI_F2_MLP) {  // (its reductions, too, at the group's end: the default path's sums)
-          defer_prev();
+                                  e->brecp(g, b), n, 1.f / (float)HW, 1};
+        } else {
           RC(ca_bwd_du_launch(g16 ? static_cast<const void*>(ghb) : ghf, g16, e->pacc, nstrips, e->recp(g, b),
-                              prm + r.ca_w1, prm + r.ca_w2, n, HW, 64, R, du, e->brecp(g, b), e->f32, st, nullptr,
-                              nullptr));
-        } else {  // (the reductions riding, as the default path's MLP launch carries them)
-          RC(ca_bwd_du_launch(g16 ? static_cast<const void*>(ghb) : ghf, g16, e->pacc, nstrips, e->recp(g, b),
-                              prm + r.ca_w1, prm + r.ca_w2, n, HW, 64, R, du, e->brecp(g, b), e->f32, st,
-                              have_prev ? &prev2 : nullptr, have_prev ? &prev1 : nullptr));
-          have_prev = false;
+                              prm + r.ca_w1, prm + r.ca_w2, n, HW, 64, R, du, e->brecp(g, b), e->f32, st));
         }
         RC(dgrad_with_wgrad(e, cp, epi, wp, 2, st));
         if (e->trace) {
@@ -1029,17 +987,15 @@ static int backward_impl(srmi_engine* e, const float* prm, const float* lr, cons
                             (last && g == 0) ? e->dRESf : nullptr, last ? nullptr : e->Um(g, b - 1),
                             last ? nullptr : e->pacc, 1.f);
         RC(wgrad_params(e, r.c1, e->hb(g, b - 1), dz, n, h, w, grads, true, 1.f, rs1, e->slab_r(b, 1),
-                        e->bslab_r(b, 1), e->slab_r_floats, e->bslab_r_floats, &wp, &red1, kSlab16));
+                        e->bslab_r(b, 1), e->slab_r_floats, e->bslab_r_floats, &wp, &red1, true));
         RC(dgrad_with_wgrad(e, cp, epi, wp, 1, st));
         if (e->trace) {
           RC(trace_copy(e, SRMI_TRACE_STREAM, g, b - 1, gstream, n, st));
           if (!last) RC(trace_copy(e, SRMI_TRACE_PACC, g, b - 1, e->pacc, n, st));
         }
-        prev2 = red2;
-        prev1 = red1;
-        have_prev = true;
+        group_sets.push_back(red2);
+        group_sets.push_back(red1);
       }
-      defer_prev();
       if (!group_sets.empty()) RC(wgrad_reduce_sets_launch(group_sets.data(), (int)group_sets.size(), st));
       // per-RCAB slots of recp / brecp (N x 160 and N x 224 floats at any CR <= 32)
       RC(ca_param_grads_batched_launch(e->recp(g, 1), e->brecp(g, 1), nb, n, (size_t)e->N * 160, (size_t)e->N * 224,
@@ -1204,7 +1160,7 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
     WgradParams wp;
     ReduceSet red;
     RC(wgrad_params(e, r.c2, e->Tm(0, b), e->DU, n, e->h, e->w, e->slab, false, 1.f, rcab_row_splits(e, n, 2),
-                    e->slab_r(b, 0), e->bslab_r(b, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red, kSlab16));
+                    e->slab_r(b, 0), e->bslab_r(b, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red, true));
     if (which == 7)  // how the RCAB backward launches run: fused | bf16 partial slabs | du formed in F2
       return (rcab_bwd_fusable(cp, wp) ? 1 : 0) | (wp.slab16 ? 2 : 0) | (du_in_f2(e, cp, wp, epi) ? 4 : 0);
     return du_in_f2(e, cp, wp, epi) ? 1 : 0;
@@ -1225,14 +1181,14 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
     cp = dgrad_params(e, r.c2, e->DU, n, h, w, &epi, e->DZ, nullptr, nullptr, nullptr, nullptr, e->Tm(0, b), nullptr,
                       1.f);
     RC(wgrad_params(e, r.c2, e->Tm(0, b), e->DU, n, h, w, grads, false, 1.f, rcab_row_splits(e, n, 2),
-                    e->slab_r(b, 0), e->bslab_r(b, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red, kSlab16));
+                    e->slab_r(b, 0), e->bslab_r(b, 0), e->slab_r_floats, e->bslab_r_floats, &wp, &red, true));
     // (as backward_impl: the CA backward and du inside the fused launch; its record and dm
     //  go to brec, which the engine's next backward rewrites)
     if (e->probe_prm && du_in_f2(e, cp, wp, epi)) {
       cp.x = wp.dy = e->GBb;
       cp.gx = wp.gx = CaBwdIn{e->pacc, conv3x3_nstrips(h, w), e->recp(0, b), e->probe_prm + r.ca_w1,
                               e->probe_prm + r.ca_w2, 64 / e->P.cfg.reduction, e->brecp(0, b), n, 1.f / (float)(h * w),
-                              SRMI_F2_MLP};
+                              1};
     }
   } else {
     const bool last = (b == 1);
@@ -1244,7 +1200,7 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream) {
       cp = dgrad_params(e, r.c1, e->DZ, n, h, w, &epi, last ? e->GAb : nullptr, ghf, ghf, last ? e->GAf : nullptr,
                         nullptr, last ? nullptr : e->Um(0, b - 1), last ? nullptr : e->pacc, 1.f);
     RC(wgrad_params(e, r.c1, e->hb(0, b - 1), e->DZ, n, h, w, grads, true, 1.f, rcab_row_splits(e, n, 1),
-                    e->slab_r(b, 1), e->bslab_r(b, 1), e->slab_r_floats, e->bslab_r_floats, &wp, &red, kSlab16));
+                    e->slab_r(b, 1), e->bslab_r(b, 1), e->slab_r_floats, e->bslab_r_floats, &wp, &red, true));
   }
   for (int i = 0; i < reps; ++i) RC(dgrad_with_wgrad(e, cp, epi, wp, which, S_(stream)));
   return 0;

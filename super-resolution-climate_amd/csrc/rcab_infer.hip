@@ -13,10 +13,10 @@
 // the CA pass reading u, h and writing h'): per image 0.6 MB less traffic and no
 // elementwise pass.  It differs from them in summation order only (m from t's
 // statistics instead of the pooled u): like them it rounds u to bf16 before
-// h' = h + s * bf16(u) (SRMI_INFER_BF16U=1, the default; the =0 variant adds the fp32 u
-// instead), within bf16 noise of the fp64 oracle
+// h' = h + s * bf16(u), within bf16 noise of the fp64 oracle
 // (test_fused_inference_rcab_matches_three_launches_and_oracle).
-// (write-back stores and the deferred conv1 epilogue: tuning.hpp SRMI_INFER_*)
+// (write-back stores: tuning.hpp SRMI_INFER_WT; SRMI_TU_INFER also selects the deferred
+//  conv1 epilogue, conv64_body.hpp conv64_defers)
 #define SRMI_TU_INFER 1
 #include "conv64_body.hpp"
 #include "ca_scale.hpp"

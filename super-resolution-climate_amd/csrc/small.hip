@@ -14,7 +14,6 @@
 
 #include "common.hpp"
 #include "srmi_internal.hpp"
-#include "wgrad_reduce.hpp"
 #include "ca_bwd.hpp"
 
 namespace srmi {
@@ -1361,29 +1360,15 @@ int ca_fwd_launch(const void* u, const float* part, int nstrips, const float* w1
 // brec per image: dz2[C] dz1[CR] dbconv2[C]; followed (after all N images) by
 // dm[N][C] = W1^T dz1 (the gradient of the pooled mean).
 // du = g * s + dm / HW  (operand type T); g fp32, or (TG = bf16_t) the bf16 engine's
-// in-group gradient stream.  DU = false (du null): the MLP backward and brec only, one
-// block per image -- the next fused backward launch forms du from g itself (ConvParams
-// gx_*, du_from_g8: the same fma and rounding)
-//
-// Rows blockIdx.y >= N of the grid (nred > 0) carry the fixed-order slab
-// reductions of the previous RCAB's two filter gradients (r0, r1: nred blocks
-// each, 256-thread wgrad_reduce_body): both are memory-bound passes of many small
-// blocks, so the reduction rides in this launch instead of a launch of its own.
-template <typename T, typename TG, bool DU = true>
+// in-group gradient stream.  (The fused conv2 backward runs the same MLP and forms du from
+// g itself, ConvParams gx, du_from_g8: the same fma and rounding.  This launch is the
+// SRMI_FLAG_DU_PASS, exact-fp32 and unfusable-shape form.)
+template <typename T, typename TG>
 __global__ void __launch_bounds__(256) ca_bwd_du_kernel(const TG* __restrict__ g, const float* __restrict__ part,
                                                         int nstrips, const float* __restrict__ rec,
                                                         const float* __restrict__ w1, const float* __restrict__ w2,
                                                         int N, int HW, int C, int CR, T* __restrict__ du,
-                                                        float* __restrict__ brec, ReduceSet r0, ReduceSet r1,
-                                                        int nred) {
-  if ((int)blockIdx.y >= N) {
-    const int id = ((int)blockIdx.y - N) * (int)gridDim.x + (int)blockIdx.x;
-    if (id < nred)
-      wgrad_reduce_body<16>(r0, id);
-    else if (id < 2 * nred)
-      wgrad_reduce_body<16>(r1, id - nred);
-    return;
-  }
+                                                        float* __restrict__ brec) {
   __shared__ float sm[kCaBwdScratch];
   const int n = blockIdx.y, tid = threadIdx.x;
   const CaBwdIn cb{part, nstrips, rec, w1, w2, CR, brec, N, 1.f / (float)HW};
@@ -1396,7 +1381,7 @@ __global__ void __launch_bounds__(256) ca_bwd_du_kernel(const TG* __restrict__ g
   float4 g0[kCaVec], g1[kCaVec];
   [[maybe_unused]] uint4 gq[kCaVec];
 #pragma unroll
-  for (int k = 0; k < (DU ? kCaVec : 0); ++k) {  // clamped, unconditional (tail lanes store nothing)
+  for (int k = 0; k < kCaVec; ++k) {  // clamped, unconditional (tail lanes store nothing)
     const size_t e = base + min(v0 + (size_t)k * blockDim.x, nv - 1) * 8;
     if constexpr (sizeof(TG) == 2) {
       gq[k] = *reinterpret_cast<const uint4*>(g + e);  // 8 bf16, decoded where used
@@ -1409,7 +1394,6 @@ __global__ void __launch_bounds__(256) ca_bwd_du_kernel(const TG* __restrict__ g
   ca_bwd_mlp(cb, n, tid, q, sm, blockIdx.x == 0);
   const float* s = sm + kCaBwdS;
   const float* dm = sm + kCaBwdDm;
-  if constexpr (!DU) return;
   const auto rdu = wt_rsrc(du, (uint32_t)((size_t)gridDim.y * HW * C * sizeof(T)));  // lane-contiguous: write-through
 #pragma unroll
   for (int k = 0; k < kCaVec; ++k) {
@@ -1438,33 +1422,20 @@ __global__ void __launch_bounds__(256) ca_bwd_du_kernel(const TG* __restrict__ g
 }
 
 int ca_bwd_du_launch(const void* g, int g16, const float* part, int nstrips, const float* rec, const float* w1,
-                     const float* w2, int N, int HW, int C, int R, void* du, float* brec, int f32, hipStream_t st,
-                     const ReduceSet* red0, const ReduceSet* red1) {
+                     const float* w2, int N, int HW, int C, int R, void* du, float* brec, int f32, hipStream_t st) {
   if (f32 && g16) return SRMI_ERR_ARG;
   if (C != 64 || C % R || (C / R) > 32 || (C / R) % 4 || (HW * C) % 8) return SRMI_ERR_SHAPE;
-  if ((red0 == nullptr) != (red1 == nullptr)) return SRMI_ERR_ARG;
-  if (red0 && (red0->Cout != red1->Cout)) return SRMI_ERR_SHAPE;
-  // (a set with neither gw nor gb -- the group tail's single reduction -- adds no blocks)
-  const bool two = red1 && (red1->gw || red1->gb);
-  if (!du && (f32 || !g16)) return SRMI_ERR_ARG;  // (du from g: the bf16 stream only)
-  const int gx = du ? ca_grid_x(HW, C) : 1;
-  const ReduceSet none{};
-  const int nred = red0 ? wgrad_reduce_blocks(red0->Cout) : 0;
-  const dim3 grid(gx, N + ((two ? 2 : 1) * nred + gx - 1) / gx);
-  const ReduceSet& a = red0 ? *red0 : none;
-  const ReduceSet& b = red1 ? *red1 : none;
+  if (!du) return SRMI_ERR_ARG;
+  const dim3 grid(ca_grid_x(HW, C), N);
   if (f32)
     hipLaunchKernelGGL((ca_bwd_du_kernel<float, float>), grid, dim3(256), 0, st, static_cast<const float*>(g), part,
-                       nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<float*>(du), brec, a, b, nred);
-  else if (g16 && !du)
-    hipLaunchKernelGGL((ca_bwd_du_kernel<bf16_t, bf16_t, false>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(g),
-                       part, nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<bf16_t*>(du), brec, a, b, nred);
+                       nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<float*>(du), brec);
   else if (g16)
     hipLaunchKernelGGL((ca_bwd_du_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(g),
-                       part, nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<bf16_t*>(du), brec, a, b, nred);
+                       part, nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<bf16_t*>(du), brec);
   else
     hipLaunchKernelGGL((ca_bwd_du_kernel<bf16_t, float>), grid, dim3(256), 0, st, static_cast<const float*>(g), part,
-                       nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<bf16_t*>(du), brec, a, b, nred);
+                       nstrips, rec, w1, w2, N, HW, C, C / R, static_cast<bf16_t*>(du), brec);
   SRMI_CHECK_LAUNCH();
   return 0;
 }

@@ -52,7 +52,7 @@ struct CaScale {
   int CR;
   float* rec;         // out: m | z1 | s per image [N][128 + CR]
   unsigned long long* stamps;  // diagnostic build only: phase stamps of ca_scale_finish (null)
-  // Partial means (training, SRMI_CA_MPART): conv1 (EPI_RELU_POOL with cas_on) writes, per
+  // Partial means (training): conv1 (EPI_RELU_POOL with cas_on) writes, per
   // workgroup (run) of an image, the matvec of its rows' share of S_tap (ca_matvec) into
   // mpart [N][nruns][64]; conv2 then sums them instead of computing the scale from t.
   float* mpart;
@@ -76,6 +76,7 @@ struct CaBwdIn {
   float inv_hw;        // 1 / (H W)
   int mlp;             // 1: every workgroup runs its image's MLP (ca_bwd_mlp; the first dgrad run
                        // of the image writes brec); 0: s and dm are read (rec, brec: an MLP launch ran)
+                       // (the engine passes 1; removing the field changes F2's code: a same-box A/B first)
 };
 
 struct ConvParams {
@@ -161,18 +162,15 @@ int wgrad3x3_nslabs(const WgradParams& p);
 int wgrad3x3_slab_layout(const WgradParams& p);
 // slab reduction into the torch-layout grad [Cout][64][3][3] (+ bias [Cout]);
 // ps != 0 un-permutes the packed PixelShuffle channel order (c'' = 64q + c -> 4c + q)
-
-int wgrad_reduce2_launch(const ReduceSet& r0, const ReduceSet& r1, hipStream_t st);
-// n independent slab reductions (equal Cout) in one launch (blockIdx.y selects the set)
-int wgrad_reduce_sets_launch(const ReduceSet* sets, int n, hipStream_t st);
-// fused RCAB backward launch: dgrad conv (epi RELUMASK / DG_ACC_CA / DG_ACC, its runs
-// sized for conv_cus CUs) beside the filter gradient wp of the same conv (wgrad48)
-int rcab_bwd_fusable(const ConvParams& cp, const WgradParams& wp);
-int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradParams& wp, hipStream_t st);
-// the fused conv2 backward (EPI_DG_RELUMASK) of this build forms du from g (ConvParams gx_*)
-bool rcab_bwd_du_from_g();
 int wgrad_reduce_launch(const float* slab, const float* bslab, int nslab, int Cout, int ps, int layout, float alpha,
                         float* gw, float* gb, hipStream_t st, int slab16 = 0);
+// n independent slab reductions (equal Cout) in one launch (blockIdx.y selects the set)
+int wgrad_reduce_sets_launch(const ReduceSet* sets, int n, hipStream_t st);
+// fused RCAB backward launch: dgrad conv (epi DG_RELUMASK / DG_ACC_CA16 / DG_CA16 /
+// DG_ACC_G1, its runs sized for conv_cus CUs) beside the filter gradient wp of the same
+// conv (wgrad48); with cp.gx / wp.gx the DG_RELUMASK launch forms du from g
+int rcab_bwd_fusable(const ConvParams& cp, const WgradParams& wp);
+int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradParams& wp, hipStream_t st);
 
 // small-channel kernels (head / tail), bicubic resampling, loss, CA, Adam, packing
 // f32 != 0: the operand-type outputs / inputs below are fp32 (exact-fp32 engine mode)
@@ -222,11 +220,9 @@ int ca_fwd_launch(const void* u, const float* part, int nstrips, const float* w1
                   const float* w2, const float* b2, int N, int HW, int C, int R, const float* h_in, float* h_out,
                   void* hb_out, float* rec, int f32, hipStream_t st, const void* hi_in = nullptr,
                   const void* lo_in = nullptr, void* lo_out = nullptr);
-// red0/red1 (both or neither): two slab reductions carried in the same launch
 // g: fp32, or (g16) the bf16 engine's in-group gradient stream in bf16
 int ca_bwd_du_launch(const void* g, int g16, const float* part, int nstrips, const float* rec, const float* w1,
-                     const float* w2, int N, int HW, int C, int R, void* du, float* brec, int f32, hipStream_t st,
-                     const ReduceSet* red0 = nullptr, const ReduceSet* red1 = nullptr);
+                     const float* w2, int N, int HW, int C, int R, void* du, float* brec, int f32, hipStream_t st);
 // inference RCAB, one launch with a workgroup per image (rcab_infer.hip): c1 = conv1
 // (yb = t), c2 = conv2 (its bias = the CA's bc2); t's per-strip sums into part, the CA
 // scale into rec, h' = h + s u into the pair hi_out / lo_out (h from h_in or the pair)

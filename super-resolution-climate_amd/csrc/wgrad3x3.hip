@@ -26,7 +26,6 @@
 #include "common.hpp"
 #include "conv64_body.hpp"
 #include "srmi_internal.hpp"
-#include "wgrad_reduce.hpp"
 
 namespace srmi {
 
@@ -546,7 +545,7 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
         if constexpr (kMain) {
           // (gx) du of pair j+1 behind K-step 0's MFMAs: in flight may stay pair j+2 and the
           // 3 groups of pair j+PF issued above; the barrier of K-step 1 publishes it
-          if (SRMI_GX_INLOOP != 0 && kc == 0 && gx && more) {
+          if (kc == 0 && gx && more) {
             if (j + 2 < np) wait_groups(1, pf ? 3 : 0);
             else wait_groups(0, 0);
             gx_pair(j + 1);
@@ -557,9 +556,6 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
           // flight may stay: pair j+2 (whole) and the 5 groups of pair j+PF issued above.
           if (j + 2 < np) wait_groups(1, pf ? 5 : 0);
           else wait_groups(0, 0);
-          if constexpr (kMain && !SRMI_GX_INLOOP) {
-            if (gx && more) gx_pair(j + 1);
-          }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
@@ -653,7 +649,8 @@ __global__ void __launch_bounds__(kWgradNW * 64, 1) wgrad48_kernel(WgradParams p
 // tail > 0 (paired map only): the filter-gradient half finishes earlier than the
 // dgrad half (F1: 24.7 vs 36.9 us at C2), so the last `tail` strips of dgrad run k
 // move to the workgroup of chunk k, which runs them before its chunk (same rows, same
-// XCD), with its own filter prologue (SRMI_FUSE_TAIL_FIRST; after it: 0).
+// XCD), with its own filter prologue: the chunk's slab stores then do not meet the dgrad
+// runs' loads.
 template <int EPI, int NW>
 __global__ void __launch_bounds__(NW * 64, 1) rcab_bwd_kernel(ConvParams cp, int run_len, int nconv, WgradParams wp,
                                                               int nwg, int paired, int tail) {
@@ -674,23 +671,13 @@ __global__ void __launch_bounds__(NW * 64, 1) rcab_bwd_kernel(ConvParams cp, int
     return;
   }
   const int nch = wp.N * wp.row_splits;
-#if SRMI_FUSE_TAIL_FIRST
   if (tail > 0) {
     conv64_body<48, EPI, NW>(cp, run_len, w, smem, tail, true);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // every wave is past its last LDS access of the strips
   }
   wgrad48_dispatch<NW, EPI == EPI_DG_RELUMASK>(wp, smem, w % nch, w / nch);
-#else
-  wgrad48_dispatch<NW, EPI == EPI_DG_RELUMASK>(wp, smem, w % nch, w / nch);
-  if (tail > 0) {
-    __syncthreads();  // every wave is past its last LDS read of the chunk
-    conv64_body<48, EPI, NW>(cp, run_len, w, smem, tail, true);
-  }
-#endif
 }
-
-bool rcab_bwd_du_from_g() { return conv64_defers<EPI_DG_RELUMASK>(); }
 
 int rcab_bwd_fusable(const ConvParams& cp, const WgradParams& wp) {
   return !cp.f32 && !wp.f32 && cp.Cin == 64 && cp.Cout == 64 && cp.in_mode == IN_PLAIN && cp.W == 48 &&
@@ -713,7 +700,7 @@ int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradPara
   if ((cp.gx.rec != nullptr) != (wp.gx.rec != nullptr) ||
       (cp.gx.rec && std::memcmp(&cp.gx, &wp.gx, sizeof(CaBwdIn)) != 0))
     return SRMI_ERR_ARG;
-  if (cp.gx.rec && (epi != EPI_DG_RELUMASK || !conv64_defers<EPI_DG_RELUMASK>() || cp.x != wp.dy ||
+  if (cp.gx.rec && (epi != EPI_DG_RELUMASK || cp.x != wp.dy ||
                     !cp.gx.part || !cp.gx.w1 || !cp.gx.w2 || !cp.gx.brec || cp.gx.CR < 4 || cp.gx.CR > 32 ||
                     cp.gx.CR % 4 || cp.Cin != 64))
     return SRMI_ERR_ARG;
@@ -737,18 +724,12 @@ int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradPara
       nconv == nwg && cp.N == wp.N && runs_per_col == wp.row_splits && run_len * kTH == wp.H / wp.row_splits;
   // dgrad strips per run handed to the paired filter-gradient workgroup (see the kernel)
   // (one strip in F1; none in F2, whose ReLU-mask strip is cheaper than the extra
-  //  filter prologue, nor in F1 with its epilogue deferred: SRMI_F1_DEFER_TAIL)
-  const bool f1_defer = epi == EPI_DG_ACC_CA16 && conv64_defers<EPI_DG_ACC_CA16>();
-  const int tail = !paired ? 0 : std::min(run_len - 1, epi == EPI_DG_RELUMASK ? 0 : (f1_defer ? SRMI_F1_DEFER_TAIL : 1));
+  //  filter prologue)
+  const int tail = !paired ? 0 : std::min(run_len - 1, epi == EPI_DG_RELUMASK ? 0 : 1);
   switch (epi) {
     case EPI_DG_RELUMASK:
       if (!c.aux) return SRMI_ERR_ARG;
       hipLaunchKernelGGL((rcab_bwd_kernel<EPI_DG_RELUMASK, kFuseNW>), grid, dim3(kFuseNW * 64), lds, st, c, run_len,
-                         nconv, w, nwg, paired, tail);
-      break;
-    case EPI_DG_ACC_CA:
-      if (!c.r1 || !c.aux || !c.part || c.yb || c.r2 || c.r3 || !c.yf || c.r1b) return SRMI_ERR_ARG;
-      hipLaunchKernelGGL((rcab_bwd_kernel<EPI_DG_ACC_CA, kFuseNW>), grid, dim3(kFuseNW * 64), lds, st, c, run_len,
                          nconv, w, nwg, paired, tail);
       break;
     case EPI_DG_ACC_CA16:
@@ -766,11 +747,9 @@ int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradPara
       hipLaunchKernelGGL((rcab_bwd_kernel<EPI_DG_CA16, kFuseNW>), grid, dim3(kFuseNW * 64), lds, st, c, run_len,
                          nconv, w, nwg, paired, tail);
       break;
-    case EPI_DG_ACC:
-      if ((!c.yf && !c.yb) || (c.part && !c.aux) || (c.r1 && c.r1b)) return SRMI_ERR_ARG;
-      hipLaunchKernelGGL((rcab_bwd_kernel<EPI_DG_ACC, kFuseNW>), grid, dim3(kFuseNW * 64), lds, st, c, run_len, nconv, w, nwg, paired, tail);
-      break;
     default:
+      // (EPI_DG_ACC_CA, EPI_DG_ACC: the fp32 gradient stream never fuses, and the bf16 engine's
+      //  dgrad_params resolves every fusable F1 to one of the three forms above)
       return SRMI_ERR_ARG;
   }
   SRMI_CHECK_LAUNCH();
@@ -810,14 +789,138 @@ int wgrad3x3_launch(const WgradParams& p, hipStream_t st) {
   return 0;
 }
 
-__global__ void __launch_bounds__(kRedQ * kRedPh) wgrad_reduce_kernel(ReduceSet r) {
-  wgrad_reduce_body<kRedPh>(r, blockIdx.x);
+// -------------------------------------------------------------------- reduce
+// block = kRedQ output quads (4*kRedQ consecutive outputs, float4 loads) x kRedPh
+// slab phases (512 threads); phase q sums slabs q, q+kRedPh, ... with 4
+// independent accumulators (4 loads in flight), then the kRedPh x 4 partials are
+// combined in a fixed 2-level order (deterministic).  64 outputs per block -> 576
+// blocks for a 64->64 conv (the former 256-output blocks left 112 CUs idle).
+// The bias slab ([nslab][Cout]) is handled by the last block(s).
+constexpr int kRedQ = 16, kRedPh = 32;
+// blocks of one slab reduction (Cout * 576 weights + Cout biases, kRedQ quads each)
+inline int wgrad_reduce_blocks(int Cout, int Q = kRedQ) { return Cout * 576 / (4 * Q) + (Cout + 4 * Q - 1) / (4 * Q); }
+
+// PH = slab phases per block (blockDim = Q * PH: 512 threads);
+// bid = this block's index within the reduction's wgrad_reduce_blocks(Cout)
+// slab16: the weight slabs are bf16 (4 values per 8-byte load), summed in fp32
+// (Q = output quads per block: kRedQ, or more quads and fewer phases for long runs of
+//  reductions, wgrad_reduce_sets_kernel)
+template <int PH, int Q = kRedQ>
+__device__ __forceinline__ void wgrad_reduce_body(const ReduceSet& rs, int bid) {
+  const float* __restrict__ slab = rs.slab;
+  const float* __restrict__ bslab = rs.bslab;
+  const int nslab = rs.nslab, Cout = rs.Cout, ps = rs.ps, layout = rs.layout;
+  const float alpha = rs.alpha;
+  float* __restrict__ gw = rs.gw;
+  float* __restrict__ gb = rs.gb;
+  __shared__ float4 red[PH][Q], red2[4][Q];
+  const int per = Cout * 576;
+  const int nwb = per / (4 * Q);  // weight blocks (per % (4 Q) == 0: Cout % 64 == 0, Q | 576)
+  const int qd = threadIdx.x % Q, ph = threadIdx.x / Q;
+  const bool is_w = bid < nwb;
+  const float* src;
+  int stride, o4, valid;
+  if (is_w) {
+    if (!gw) return;
+    o4 = bid * (4 * Q) + qd * 4;
+    src = slab + o4;
+    stride = per;
+    valid = 1;
+  } else {
+    if (!gb) return;
+    o4 = (bid - nwb) * (4 * Q) + qd * 4;
+    src = bslab + o4;
+    stride = Cout;
+    valid = o4 < Cout;
+  }
+  float4 a[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (valid && is_w && rs.slab16) {  // (uniform) bf16 weight slabs: the same order and sums
+    const uint16_t* src16 = reinterpret_cast<const uint16_t*>(slab) + o4;
+    constexpr int U = 4;
+    for (int k = ph; k < nslab; k += U * PH) {
+      uint2 v[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const int sl = k + j * PH;
+        v[j] = *reinterpret_cast<const uint2*>(src16 + (size_t)min(sl, nslab - 1) * stride);
+        if (sl >= nslab) v[j] = make_uint2(0u, 0u);  // (bf16 +0)
+      }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        a[j].x += bf2f(v[j].x & 0xFFFFu); a[j].y += bf2f(v[j].x >> 16);
+        a[j].z += bf2f(v[j].y & 0xFFFFu); a[j].w += bf2f(v[j].y >> 16);
+      }
+    }
+  } else if (valid) {
+    // phase ph sums slabs ph, ph + PH, ... -- U loads in flight per round,
+    // clamped + zeroed past the end (adding 0.f is exact; no divergent branch)
+    constexpr int U = 4;
+    for (int k = ph; k < nslab; k += U * PH) {
+      float4 v[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const int sl = k + j * PH;
+        v[j] = *reinterpret_cast<const float4*>(src + (size_t)min(sl, nslab - 1) * stride);
+        if (sl >= nslab) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        a[j].x += v[j].x; a[j].y += v[j].y; a[j].z += v[j].z; a[j].w += v[j].w;
+      }
+    }
+  }
+  red[ph][qd] = make_float4((a[0].x + a[1].x) + (a[2].x + a[3].x), (a[0].y + a[1].y) + (a[2].y + a[3].y),
+                            (a[0].z + a[1].z) + (a[2].z + a[3].z), (a[0].w + a[1].w) + (a[2].w + a[3].w));
+  __syncthreads();
+  // fixed-order 2-level combine of the PH phase partials
+  constexpr int L1 = 4, PER = PH / L1;
+  if (ph < L1) {
+    float4 r = red[ph][qd];
+#pragma unroll
+    for (int q = 1; q < PER; ++q) {
+      const float4 t = red[ph + q * L1][qd];
+      r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
+    }
+    red2[ph][qd] = r;
+  }
+  __syncthreads();
+  if (ph != 0 || !valid) return;
+  float4 r = red2[0][qd];
+#pragma unroll
+  for (int q = 1; q < L1; ++q) {
+    const float4 t = red2[q][qd];
+    r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
+  }
+  const float s4[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int o = o4 + e;
+    if (is_w) {
+      int cop, ci, tap;
+      if (layout == 1) {  // wgrad48 native order [cb][wave][t][ct][lane][4]
+        const int cb = o / (64 * 576), l = o - cb * (64 * 576);
+        const int r = l & 3, lane = (l >> 2) & 63, ct = (l >> 8) & 3, wt = l >> 10;
+        const int wave = wt / 9, j = wt;  // j = 9 * wave + t
+        tap = j >> 2;
+        ci = (j & 3) * 16 + (lane & 15);
+        cop = cb * 64 + ((ct + wave) & 3) * 16 + 4 * (lane >> 4) + r;
+      } else {  // [tap][ci][Cout]
+        cop = o % Cout;
+        ci = (o / Cout) & 63;
+        tap = o / (Cout * 64);
+      }
+      const int cot = ps ? (4 * (cop & 63) + (cop >> 6)) : cop;
+      gw[((size_t)cot * 64 + ci) * 9 + tap] = alpha * s4[e];
+    } else if (o < Cout) {
+      const int cot = ps ? (4 * (o & 63) + (o >> 6)) : o;
+      gb[cot] = alpha * s4[e];
+    }
+  }
 }
 
-// two independent reductions in one launch (blockIdx.y selects the set): the two
-// filter gradients of an RCAB on the side stream share one launch and one boundary
-__global__ void __launch_bounds__(kRedQ * kRedPh) wgrad_reduce2_kernel(ReduceSet r0, ReduceSet r1) {
-  const ReduceSet& r = blockIdx.y ? r1 : r0;
+__global__ void __launch_bounds__(kRedQ * kRedPh) wgrad_reduce_kernel(ReduceSet r) {
   wgrad_reduce_body<kRedPh>(r, blockIdx.x);
 }
 
@@ -855,14 +958,6 @@ int wgrad_reduce_sets_launch(const ReduceSet* sets, int n, hipStream_t st) {
                        dim3(kSetQ * kSetPh), 0, st, r);
     SRMI_CHECK_LAUNCH();
   }
-  return 0;
-}
-
-int wgrad_reduce2_launch(const ReduceSet& r0, const ReduceSet& r1, hipStream_t st) {
-  if (r0.Cout % 64 || r1.Cout != r0.Cout) return SRMI_ERR_SHAPE;
-  const int blocks = wgrad_reduce_blocks(r0.Cout);
-  hipLaunchKernelGGL(wgrad_reduce2_kernel, dim3(blocks, 2), dim3(kRedQ * kRedPh), 0, st, r0, r1);
-  SRMI_CHECK_LAUNCH();
   return 0;
 }
 

@@ -54,7 +54,7 @@ def test_pooled_mean_from_t_statistics(C, H, W):
 
 def _partial_share(t, w, y0, y1, x0, x1):
     """The share of sum_{tap, ci} W2 S_tap of the rows y0..y1-1 and columns x0..x1-1 of t,
-    as one conv1 workgroup forms it in the training forward (conv64_body, SRMI_CA_MPART):
+    as one conv1 workgroup forms it in the training forward (conv64_body, CaPart):
     T over its tile, the image's column 0 / W-1 restricted to its rows (only when its
     tile holds them), rows 0 / H-1 and the corners only where its tile holds them."""
     C, H, W = t.shape

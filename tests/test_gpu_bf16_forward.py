@@ -144,7 +144,7 @@ def test_residual_pair_closes(train, hw, cb, B, cu, flags, cap):
     plus the codec's 128 fp32 steps, h_in the fp32 group input (b = 1) or the decoded pair
     before; hi == (A' + 0x8000) >> 16 bit for bit.  u is the stored bf16 u in training and
     bf16(conv2_fp64(t) + b2), or a bf16 neighbour the accumulation bound admits, in inference:
-    the engine adds s bf16(u), in the one-launch RCAB too (SRMI_INFER_BF16U = 1) -- with the
+    the engine adds s bf16(u), in the one-launch RCAB too -- with the
     fp32 u the elements would be off by up to half a bf16 ulp of u times s, between the
     candidates and far outside this bound."""
     _check("e", (train, hw, cb, B, cu, flags, cap))

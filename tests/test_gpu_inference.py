@@ -178,8 +178,8 @@ def test_fused_inference_rcab_matches_three_launches_and_oracle(C, nl, nb, hw, N
     image and the CA MLP -> conv2 whose epilogue writes h + s u; u is never stored)
     against the three launches (SRMI_FLAG_NO_RCAB_INFER: conv1, conv2 + pool, CA pass)
     and the fp64 oracle forward.  The one launch differs from the three only in the
-    summation order of mean(u): like them it adds s bf16(u) to h (SRMI_INFER_BF16U = 1;
-    test_gpu_bf16_forward.test_residual_pair_closes holds the pair to that, element by
+    summation order of mean(u): like them it adds s bf16(u) to h
+    (test_gpu_bf16_forward.test_residual_pair_closes holds the pair to that, element by
     element), so both sit within bf16 noise of the oracle and of each other.  cb: the CA
     bottleneck (CR = 64 / cb = 32, 8, 4)."""
     from srmi._lib import SRMI_FLAG_NO_RCAB_INFER

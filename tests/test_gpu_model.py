@@ -411,7 +411,7 @@ def _engine_variants_agree(lr_hw, flags, grad_tol, fwd_tol=None, cb=2):
 def test_ca_forward_in_conv2_matches_ca_pass(lr_hw):
     """The training CA forward inside conv2's launch (the default: conv1 writes t, the
     per-strip sums of the bf16 t and per workgroup its rows' share of mean(u) -- the
-    matvec on conv2's bf16 filter image, SRMI_CA_MPART; every conv2 workgroup sums the
+    matvec on conv2's bf16 filter image; every conv2 workgroup sums the
     shares, runs the CA MLP and writes u and h' = h + s bf16(u); engine.cpp ca_fwd_mode)
     against the CA pass of its own (SRMI_FLAG_CA_PASS: conv2 + pool writing u, then
     ca_fwd).  mean(u) differs only in fp32 summation order, so the forward agrees far
