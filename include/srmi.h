@@ -37,6 +37,14 @@
  *                                   sres/base/source/swot/raw.py:133-145, :216-233
  *   srmi_tiles_to_region         -> denorm + assemble_images
  *                                   sres/controller/dual_trainer.py:67-77, :482-512
+ *   srmi_region_to_tiles_overlap,
+ *   srmi_tiles_blend,
+ *   srmi_overlap_count           -> generalise get_tiles (swot/raw.py:216-233) and
+ *                                   assemble_images (dual_trainer.py:482-512) to
+ *                                   overlapping tiles and a feathered blend.  The
+ *                                   reference has no overlapped form: its tiles are the
+ *                                   disjoint floor grid and its mosaic a concatenation.
+ *                                   An extension, not a parity item.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -381,6 +389,38 @@ int srmi_region_to_tiles(const float* region, int C, int H, int W, int ty, int t
  * inv == NULL: tile i is cell i */
 int srmi_tiles_to_region(const float* tiles, const float* mean, const float* std, const int* inv, int C, int ty,
                          int tx, int gy, int gx, float* out, void* stream);
+
+/* ---- overlapping tiles, blended mosaic (no reference counterpart) ------- */
+/* The plan of one axis is three integers: length L, tile t, stride S, 1 <= S <= t
+ * <= L.  It has n = ceil((L - t) / S) + 1 tiles, tile i at the origin min(i S, L - t):
+ * the last tile is shifted inward, so the axis is covered completely (a pixel may lie
+ * in three tiles of an axis even at S > t / 2).  srmi_overlap_count (host only)
+ * returns n, or SRMI_ERR_ARG for a plan outside those bounds. */
+int srmi_overlap_count(int L, int t, int S);
+/* region [C][H][W] fp32 -> tiles [ny*nx][C][ty][tx] cut at the plan's origins (tile
+ * iy * nx + ix) and normalised per tile and channel by `mode`, with the arithmetic of
+ * srmi_region_to_tiles_norm: off / div / off_out / div_out are [ny*nx][C], bad[ny*nx]
+ * (optional) = 1 where the tile holds a non-finite value.  With sy == ty, sx == tx on
+ * a region the tile divides, the result is srmi_region_to_tiles_norm's bit for bit.
+ * Any origin alignment (the float4 form is taken only where W, tx and sx are multiples
+ * of 4 and the buffers 16-byte aligned).  ny*nx <= 65535 (SRMI_ERR_SHAPE); a plan or
+ * mode out of range, or a missing buffer: SRMI_ERR_ARG. */
+int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
+                                 const float* off, const float* div, float* tiles, float* off_out, float* div_out,
+                                 int* bad, void* stream);
+/* tiles [ny*nx][C][Ty][Tx] of the plan (Ho, Ty, Sy) x (Wo, Tx, Sx) -> out [C][Ho][Wo]:
+ * out = sum_k w_k v_k / sum_k w_k over the tiles k covering the pixel with bad[k] == 0
+ * (bad == NULL: all), v = x * div + off as srmi_tiles_to_region forms it (off == NULL:
+ * no denorm), w = wy * wx with the integer ramp w(p) = min(p + 1, t - p, t - S + 1) at
+ * tile-local position p.  One thread per pixel (or quad) gathers its tiles in ascending
+ * (iy, ix) order: fp32 sums, one division, no atomics -- deterministic.  A bad tile
+ * contributes nothing and is not read; a pixel with no tile left is NaN; a pixel with
+ * exactly one is a copy of v, so at S == T on a divisible region the result is
+ * srmi_tiles_to_region's bit for bit.  At S == T on a ragged region the shifted last
+ * tile is averaged with its neighbour where the two overlap.  Ho <= 65535
+ * (SRMI_ERR_SHAPE); a plan out of range or a missing buffer: SRMI_ERR_ARG. */
+int srmi_tiles_blend(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty, int Tx,
+                     int Sy, int Sx, int Ho, int Wo, float* out, void* stream);
 
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)

@@ -1565,6 +1565,20 @@ int srmi_region_to_tiles_norm(const float* region, int C, int H, int W, int ty, 
                                      S_(stream));
 }
 
+int srmi_overlap_count(int L, int t, int S) { return overlap_count(L, t, S); }
+
+int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
+                                 const float* off, const float* div, float* tiles, float* off_out, float* div_out,
+                                 int* bad, void* stream) {
+  return region_to_tiles_overlap_launch(region, C, H, W, ty, tx, sy, sx, mode, off, div, tiles, off_out, div_out, bad,
+                                        S_(stream));
+}
+
+int srmi_tiles_blend(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty, int Tx,
+                     int Sy, int Sx, int Ho, int Wo, float* out, void* stream) {
+  return tiles_blend_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, out, S_(stream));
+}
+
 int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {
   return tile_stats_launch(tiles, n, C, ty, tx, acc, first, S_(stream));
 }

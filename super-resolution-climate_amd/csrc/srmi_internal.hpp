@@ -282,6 +282,13 @@ int batch_prep_norm_launch(const float* raw, long long B, int C, int T, int flip
 int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
                                 const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
                                 hipStream_t st);
+// overlapped tiles and their blended mosaic (tiles.hip)
+int overlap_count(long long L, long long t, long long S);
+int region_to_tiles_overlap_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
+                                   const float* off, const float* dv, float* tiles, float* off_out, float* div_out,
+                                   int* bad, hipStream_t st);
+int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
+                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

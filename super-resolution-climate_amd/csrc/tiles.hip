@@ -22,6 +22,9 @@
 // tiles_to_region replaces denorm (dual_trainer.py:67-77: x * std + mean) fused
 // with assemble_images (dual_trainer.py:482-512: tile id -> grid cell
 // (tid / gx, tid % gx), cells without a tile are NaN).
+//
+// region_to_tiles_overlap / tiles_blend generalise the cut and the mosaic to overlapping
+// tiles and a feathered blend (srmi.superres).  The reference has no overlapped form.
 #include <math.h>
 
 #include "common.hpp"
@@ -39,14 +42,16 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
   return s;
 }
 
-// grid (C, ntiles): tile t = grid cell t (row-major over gy x gx)
+// grid (C, ntiles): tile t = grid cell t (row-major over gy x gx), cut at the origin
+// min(i * stride, length - tile) per axis -- the floor grid's i * tile when the stride is
+// the tile (i < length / tile), the overlapped plan's (srmi_region_to_tiles_overlap) else
 __global__ void __launch_bounds__(256) region_to_tiles_kernel(const float* __restrict__ region, int C, int H, int W,
-                                                              int ty, int tx, int gx, float* __restrict__ tiles,
-                                                              float* __restrict__ mean, float* __restrict__ stdv,
-                                                              int* __restrict__ bad) {
+                                                              int ty, int tx, int gx, int sy, int sx,
+                                                              float* __restrict__ tiles, float* __restrict__ mean,
+                                                              float* __restrict__ stdv, int* __restrict__ bad) {
   __shared__ float red[4];
   const int c = blockIdx.x, t = blockIdx.y;
-  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  const int y0 = min((t / gx) * sy, H - ty), x0 = min((t % gx) * sx, W - tx);
   const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
   const int n = ty * tx;
   float s = 0.f;
@@ -90,12 +95,12 @@ __device__ __forceinline__ float block_sum1024(float v, float* red) {
   return s;
 }
 __global__ void __launch_bounds__(1024) region_to_tiles_reg_kernel(const float* __restrict__ region, int C, int H,
-                                                                   int W, int ty, int tx, int gx,
+                                                                   int W, int ty, int tx, int gx, int sy, int sx,
                                                                    float* __restrict__ tiles, float* __restrict__ mean,
                                                                    float* __restrict__ stdv, int* __restrict__ bad) {
   __shared__ float red[16];
   const int c = blockIdx.x, t = blockIdx.y;
-  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  const int y0 = min((t / gx) * sy, H - ty), x0 = min((t % gx) * sx, W - tx);
   const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
   const int tx4 = tx >> 2, n4 = ty * tx4, n = ty * tx;
   float4 v[kR2tKR];
@@ -137,24 +142,32 @@ __global__ void __launch_bounds__(1024) region_to_tiles_reg_kernel(const float* 
   }
 }
 
-int region_to_tiles_launch(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
-                           float* stdv, int* bad, hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
-  const int gy = H / ty, gx = W / tx;
+// gy x gx tiles at strides (sy, sx), the caller's validated plan.  The float4 form needs
+// every tile origin on a 16-byte boundary: W, tx and the x stride multiples of 4 (the
+// shifted last tile starts at W - tx).
+static int region_to_tiles_plan_launch(const float* region, int C, int H, int W, int ty, int tx, int gy, int gx,
+                                       int sy, int sx, float* tiles, float* mean, float* stdv, int* bad,
+                                       hipStream_t st) {
   if (bad) {
-    const hipError_t e = hipMemsetAsync(bad, 0, sizeof(int) * gy * gx, st);
+    const hipError_t e = hipMemsetAsync(bad, 0, sizeof(int) * (size_t)gy * gx, st);
     if (e != hipSuccess) return -(int)e;
   }
-  const bool reg = tx % 4 == 0 && W % 4 == 0 && (size_t)ty * (tx / 4) <= (size_t)1024 * kR2tKR &&
+  const bool reg = tx % 4 == 0 && W % 4 == 0 && sx % 4 == 0 && (size_t)ty * (tx / 4) <= (size_t)1024 * kR2tKR &&
                    ((uintptr_t)region & 15) == 0 && ((uintptr_t)tiles & 15) == 0;
   if (reg)
     hipLaunchKernelGGL(region_to_tiles_reg_kernel, dim3(C, gy * gx), dim3(1024), 0, st, region, C, H, W, ty, tx, gx,
-                       tiles, mean, stdv, bad);
+                       sy, sx, tiles, mean, stdv, bad);
   else
-    hipLaunchKernelGGL(region_to_tiles_kernel, dim3(C, gy * gx), dim3(256), 0, st, region, C, H, W, ty, tx, gx, tiles,
-                       mean, stdv, bad);
+    hipLaunchKernelGGL(region_to_tiles_kernel, dim3(C, gy * gx), dim3(256), 0, st, region, C, H, W, ty, tx, gx, sy,
+                       sx, tiles, mean, stdv, bad);
   SRMI_CHECK_LAUNCH();
   return 0;
+}
+
+int region_to_tiles_launch(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
+                           float* stdv, int* bad, hipStream_t st) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  return region_to_tiles_plan_launch(region, C, H, W, ty, tx, H / ty, W / tx, ty, tx, tiles, mean, stdv, bad, st);
 }
 
 // out[c][Y][X] = tiles[inv[cell]][c][y][x] * std + mean, NaN where inv[cell] < 0
@@ -509,7 +522,7 @@ constexpr int kNormKR = 9;
 // off / dv are indexed by (grid cell, channel).  kVec: the tile in registers, float4.
 template <int kMode, bool kVec>
 __global__ void __launch_bounds__(1024) region_to_tiles_norm_kernel(const float* __restrict__ region, int C, int H,
-                                                                    int W, int ty, int tx, int gx,
+                                                                    int W, int ty, int tx, int gx, int sy, int sx,
                                                                     const float* __restrict__ off,
                                                                     const float* __restrict__ dv,
                                                                     float* __restrict__ tiles,
@@ -518,7 +531,7 @@ __global__ void __launch_bounds__(1024) region_to_tiles_norm_kernel(const float*
                                                                     int* __restrict__ bad) {
   __shared__ float red[32];
   const int c = blockIdx.x, t = blockIdx.y;
-  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  const int y0 = min((t / gx) * sy, H - ty), x0 = min((t % gx) * sx, W - tx);
   const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
   const int tx4 = tx >> 2, n4 = ty * tx4, n = ty * tx;
   const size_t p = (size_t)t * C + c;
@@ -577,6 +590,33 @@ __global__ void __launch_bounds__(1024) region_to_tiles_norm_kernel(const float*
   }
 }
 
+// LSCALE / AFFINE over gy x gx tiles at strides (sy, sx); the float4 form as in
+// region_to_tiles_plan_launch
+static int region_to_tiles_norm_plan_launch(const float* region, int C, int H, int W, int ty, int tx, int gy, int gx,
+                                            int sy, int sx, int mode, const float* off, const float* dv, float* tiles,
+                                            float* off_out, float* div_out, int* bad, hipStream_t st) {
+  if (bad) {
+    const hipError_t e = hipMemsetAsync(bad, 0, sizeof(int) * (size_t)gy * gx, st);
+    if (e != hipSuccess) return -(int)e;
+  }
+  const bool vec = tx % 4 == 0 && W % 4 == 0 && sx % 4 == 0 && (size_t)ty * (tx / 4) <= (size_t)1024 * kNormKR &&
+                   ((uintptr_t)region & 15) == 0 && ((uintptr_t)tiles & 15) == 0;
+  const dim3 grid(C, gy * gx), block(1024);
+#define SRMI_R2T_NORM(MODE, VEC)                                                                                 \
+  hipLaunchKernelGGL((region_to_tiles_norm_kernel<MODE, VEC>), grid, block, 0, st, region, C, H, W, ty, tx, gx, sy, \
+                     sx, off, dv, tiles, off_out, div_out, bad)
+  if (mode == SRMI_NORM_LSCALE) {
+    if (vec) SRMI_R2T_NORM(SRMI_NORM_LSCALE, true);
+    else SRMI_R2T_NORM(SRMI_NORM_LSCALE, false);
+  } else {
+    if (vec) SRMI_R2T_NORM(SRMI_NORM_AFFINE, true);
+    else SRMI_R2T_NORM(SRMI_NORM_AFFINE, false);
+  }
+#undef SRMI_R2T_NORM
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
 int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
                                 const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
                                 hipStream_t st) {
@@ -589,24 +629,138 @@ int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty
   if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
   const int gy = H / ty, gx = W / tx;
   if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
-  if (bad) {
-    const hipError_t e = hipMemsetAsync(bad, 0, sizeof(int) * gy * gx, st);
-    if (e != hipSuccess) return -(int)e;
+  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, ty, tx, mode, off, dv, tiles, off_out,
+                                          div_out, bad, st);
+}
+
+// ------------------------------------------------ overlapped tiles, blended mosaic
+// No reference counterpart: get_tiles (raw.py:216-233) cuts the disjoint floor grid and
+// assemble_images (dual_trainer.py:482-512) concatenates it.  Here an axis of length L
+// is covered by n = ceil((L - t) / S) + 1 tiles of size t at stride S (1 <= S <= t <= L),
+// tile i at the origin min(i S, L - t): the last tile is shifted inward, so the axis is
+// covered completely.  Three scalars per axis are the whole plan; the kernels compute
+// the origins themselves.
+int overlap_count(long long L, long long t, long long S) {
+  if (S < 1 || t < S || L < t || L > 0x7fffffffLL) return SRMI_ERR_ARG;
+  const long long n = (L - t + S - 1) / S + 1;
+  return n > 0x7fffffffLL ? SRMI_ERR_ARG : (int)n;
+}
+
+int region_to_tiles_overlap_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
+                                   const float* off, const float* dv, float* tiles, float* off_out, float* div_out,
+                                   int* bad, hipStream_t st) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.x
+  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
+  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
+      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
+    return SRMI_ERR_ARG;
+  if (mode == SRMI_NORM_LNORM)
+    return region_to_tiles_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, tiles, off_out, div_out, bad, st);
+  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, mode, off, dv, tiles, off_out,
+                                          div_out, bad, st);
+}
+
+// the tiles i with origin(i) <= p < origin(i) + t are lo .. hi, without a gap: tiles
+// 0 .. n-2 sit at i S < L - t, the last one at L - t
+__device__ __forceinline__ void overlap_cover(int p, int L, int t, int S, int n, int& lo, int& hi) {
+  lo = p < t ? 0 : min((p - t) / S + 1, n - 1);
+  hi = p >= L - t ? n - 1 : p / S;
+}
+// blend weight at tile-local position q: the integer ramp min(q + 1, t - q, R + 1) with
+// R = t - S, so two regularly overlapping tiles weigh (R - q) / (R + 1) and (q + 1) /
+// (R + 1) across their overlap (never zero), and R = 0 weighs everything 1
+__device__ __forceinline__ int overlap_weight(int q, int t, int R) { return min(min(q + 1, t - q), R + 1); }
+
+// out[c][Y][X] = sum_k w_k v_k / sum_k w_k over the non-bad tiles k covering (Y, X), v =
+// tile value * div + off (off == NULL: as stored), w = wy wx.  Gather form: a thread owns
+// kV pixels of one row and walks the covering tiles in ascending (iy, ix) order (up to
+// ceil(t / S) + 1 per axis), fp32 sums, integer weight sums, one division -- no atomics,
+// deterministic.  A bad tile is skipped before anything of it is read; no cover left: NaN;
+// exactly one: its value, copied (so S == T on a divisible region is tiles_to_region,
+// bit for bit).  kV == 4: Tx, Sx, Wo multiples of 4 put every tile edge on a quad
+// boundary, so the quad has one cover and its tile rows are 16-byte aligned.
+// grid (ceil(Wo / kV / 256), Ho, C)
+template <int kV>
+__global__ void __launch_bounds__(256) tiles_blend_kernel(const float* __restrict__ tiles,
+                                                          const float* __restrict__ off,
+                                                          const float* __restrict__ dv, const int* __restrict__ bad,
+                                                          int C, int Ty, int Tx, int Sy, int Sx, int ny, int nx,
+                                                          int Ho, int Wo, float* __restrict__ out) {
+  const int X = (blockIdx.x * 256 + threadIdx.x) * kV, Y = blockIdx.y, c = blockIdx.z;
+  if (X >= Wo) return;
+  const int Ry = Ty - Sy, Rx = Tx - Sx;
+  int ylo, yhi, xlo, xhi;
+  overlap_cover(Y, Ho, Ty, Sy, ny, ylo, yhi);
+  overlap_cover(X, Wo, Tx, Sx, nx, xlo, xhi);
+  float acc[kV], one[kV];
+  int wsum[kV], cnt = 0;
+#pragma unroll
+  for (int e = 0; e < kV; ++e) {
+    acc[e] = 0.f;
+    one[e] = 0.f;
+    wsum[e] = 0;
   }
-  const bool vec = tx % 4 == 0 && W % 4 == 0 && (size_t)ty * (tx / 4) <= (size_t)1024 * kNormKR &&
-                   ((uintptr_t)region & 15) == 0 && ((uintptr_t)tiles & 15) == 0;
-  const dim3 grid(C, gy * gx), block(1024);
-#define SRMI_R2T_NORM(MODE, VEC)                                                                                 \
-  hipLaunchKernelGGL((region_to_tiles_norm_kernel<MODE, VEC>), grid, block, 0, st, region, C, H, W, ty, tx, gx, off, \
-                     dv, tiles, off_out, div_out, bad)
-  if (mode == SRMI_NORM_LSCALE) {
-    if (vec) SRMI_R2T_NORM(SRMI_NORM_LSCALE, true);
-    else SRMI_R2T_NORM(SRMI_NORM_LSCALE, false);
-  } else {
-    if (vec) SRMI_R2T_NORM(SRMI_NORM_AFFINE, true);
-    else SRMI_R2T_NORM(SRMI_NORM_AFFINE, false);
+  for (int iy = ylo; iy <= yhi; ++iy) {
+    const int qy = Y - min(iy * Sy, Ho - Ty);
+    const int wy = overlap_weight(qy, Ty, Ry);
+    for (int ix = xlo; ix <= xhi; ++ix) {
+      const int t = iy * nx + ix;
+      if (bad && bad[t]) continue;
+      const int qx = X - min(ix * Sx, Wo - Tx);
+      const size_t p = (size_t)t * C + c;
+      const float* src = tiles + (p * Ty + qy) * Tx + qx;
+      float v[kV];
+      if constexpr (kV == 4) {
+        const float4 f = *reinterpret_cast<const float4*>(src);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+      } else {
+        v[0] = src[0];
+      }
+      if (off) {
+        const float sd = dv[p], m = off[p];
+#pragma unroll
+        for (int e = 0; e < kV; ++e) v[e] = v[e] * sd + m;
+      }
+      ++cnt;
+#pragma unroll
+      for (int e = 0; e < kV; ++e) {
+        const int w = wy * overlap_weight(qx + e, Tx, Rx);
+        acc[e] = fmaf((float)w, v[e], acc[e]);
+        wsum[e] += w;
+        one[e] = v[e];
+      }
+    }
   }
-#undef SRMI_R2T_NORM
+  float r[kV];
+#pragma unroll
+  for (int e = 0; e < kV; ++e)
+    r[e] = cnt == 0 ? __int_as_float(0x7fc00000) : cnt == 1 ? one[e] : acc[e] / (float)wsum[e];
+  float* dst = out + ((size_t)c * Ho + Y) * Wo + X;
+  if constexpr (kV == 4) *reinterpret_cast<float4*>(dst) = make_float4(r[0], r[1], r[2], r[3]);
+  else dst[0] = r[0];
+}
+
+int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
+                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st) {
+  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.z
+  const int ny = overlap_count(Ho, Ty, Sy), nx = overlap_count(Wo, Tx, Sx);
+  if (ny < 0 || nx < 0) return SRMI_ERR_ARG;
+  // grid.y; the tile index and a pixel's integer weight sum (at most t / S + 2 covering
+  // tiles per axis, each weighing at most R + 1 there) stay in int
+  const long long wy = (long long)(Ty / Sy + 2) * (Ty - Sy + 1), wx = (long long)(Tx / Sx + 2) * (Tx - Sx + 1);
+  if (Ho > 65535 || (long long)ny * nx > 0x7fffffffLL || wy * wx > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (!tiles || !out || (off && !dv)) return SRMI_ERR_ARG;
+  const bool vec = Tx % 4 == 0 && Sx % 4 == 0 && Wo % 4 == 0 && ((uintptr_t)tiles & 15) == 0 &&
+                   ((uintptr_t)out & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(tiles_blend_kernel<4>, dim3((Wo / 4 + 255) / 256, Ho, C), dim3(256), 0, st, tiles, off, dv,
+                       bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, out);
+  else
+    hipLaunchKernelGGL(tiles_blend_kernel<1>, dim3((Wo + 255) / 256, Ho, C), dim3(256), 0, st, tiles, off, dv, bad, C,
+                       Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, out);
   SRMI_CHECK_LAUNCH();
   return 0;
 }

@@ -37,6 +37,7 @@ TRACE_SLOTS = {"GRB": 0, "STREAM": 1, "PACC": 2, "DZ": 3, "DU": 4}
 FWD_TRACE_SLOTS = {"LO": 0, "PPOOL": 1, "RF": 2, "HB": 3, "T": 4, "REC": 5}
 TILE_LOSS_SUB = 16  # parts per tile of srmi_tile_loss_parts
 
+SRMI_ERR_ARG = -10001
 ERRORS = {-10001: "SRMI_ERR_ARG", -10002: "SRMI_ERR_SHAPE", -10003: "SRMI_ERR_WORKSPACE",
           -10004: "SRMI_ERR_UNSUPPORTED"}
 
@@ -115,6 +116,10 @@ _SIGS = {
                              C.c_int),
     "srmi_region_to_tiles_norm": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P],
                                   C.c_int),
+    "srmi_overlap_count": ([C.c_int, C.c_int, C.c_int], C.c_int),
+    "srmi_region_to_tiles_overlap": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P,
+                                      P, P, P, P], C.c_int),
+    "srmi_tiles_blend": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "srmi_tile_stats": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, P, C.c_int, P], C.c_int),
     "srmi_tile_stats_finalize": ([P, C.c_longlong, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_llc_index_map_workspace": ([C.c_longlong, C.POINTER(C.c_size_t)], C.c_int),

@@ -183,6 +183,22 @@ def save_inference_results(path: str, var_results: Dict[str, Var], losses: Dict[
     return path
 
 
+def save_superres_results(path_for_var, images: Dict[str, object], varnames: Sequence[str],
+                          losses: Optional[Dict[str, float]] = None) -> List[str]:
+    """The three images of srmi.superres.RegionSuperResolver.super_resolve ('input'
+    [C, h, w], 'interpolated' and 'model' [C, s h, s w]) as one Image-structure file per
+    variable: image_results' [y, x] arrays through save_inference_results (the same
+    netCDF-3 writer and coercions; 'input' on ys / xs).  There is no 'target' -- a field
+    with no HR has none -- and ``losses`` is empty unless RegionSuperResolver.score
+    supplied some.  path_for_var: varname -> file path (e.g. a results_path partial).
+    No reference counterpart (its files come from process_image only)."""
+    missing = [k for k in ("input", "interpolated", "model") if k not in images]
+    if missing:
+        raise ValueError(f"super_resolve images lack {missing}")
+    per_var = image_results({k: images[k] for k in ("input", "interpolated", "model")}, varnames)
+    return [save_inference_results(path_for_var(v), per_var[v], dict(losses or {})) for v in varnames]
+
+
 def load_inference_results(path: str) -> Tuple[Dict[str, Var], Dict[str, float]]:
     """load_inference_results (inference.py:40-50): the data variables (``input``
     renamed back to y / x) and the losses dict."""

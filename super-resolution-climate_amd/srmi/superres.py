@@ -1,0 +1,273 @@
+"""Super-resolve a low-resolution region: overlapping tiles, blended into one mosaic.
+
+No reference counterpart -- a deliberate extension, not a parity item.  The reference
+(and srmi.inference.TiledInference, its drop-in) starts from a HIGH-resolution region,
+downsamples it, runs the model and scores the result against the region it started
+from: an evaluation harness.  Its tiles are the disjoint floor grid of get_tiles
+(sres/base/source/swot/raw.py:216-233) and its mosaic the plain concatenation of
+assemble_images (sres/controller/dual_trainer.py:482-512), so the rows and columns past
+the last whole tile are dropped and neighbouring tiles, each normalised and convolved
+alone with zero padding, disagree along every seam.
+
+``RegionSuperResolver`` takes the coarse field itself, [C, h, w], and returns the
+[C, s h, s w] field: the LR region is cut into overlapping tiles
+(``srmi_region_to_tiles_overlap``), the tiles go through the inference engine, and the
+outputs are blended with a feathered window (``srmi_tiles_blend``) -- full coverage,
+all on the device.
+
+The plan
+--------
+Each axis is three integers, in LR pixels for cutting and in output pixels (times the
+model scale) for blending: length ``L``, tile ``t``, stride ``S`` with 1 <= S <= t <= L;
+the overlap is ``R = t - S``.  It has ``n = ceil((L - t) / S) + 1`` tiles, tile ``i`` at
+the origin ``min(i S, L - t)``: the last tile is shifted inward, so the axis is always
+covered completely.  A pixel may be covered by THREE tiles of an axis (the shifted last
+tile next to two regular ones) whenever ``L - t - (n - 2) S < R``.
+
+The blend weight along an axis is the integer ramp ``w(p) = min(p + 1, t - p, R + 1)``
+at tile-local position ``p``; the 2-D weight is ``wy wx`` and the blended value
+``sum_k w_k v_k / sum_k w_k`` over the non-bad tiles covering the pixel.  Across a
+regular overlap the two weights are ``(R - q) / (R + 1)`` and ``(q + 1) / (R + 1)``: a
+linear ramp that never reaches zero.  With ``R = 0`` every weight is 1, so a ragged edge
+at ``R = 0`` AVERAGES the shifted last tile with its neighbour where the two overlap
+(and a region the tile divides is the plain mosaic).
+
+Bad tiles: a tile holding a non-finite value is flagged by the cut, rides through the
+forward, and is ignored by the blend (its values are never read).  A pixel whose
+covering tiles are all bad is NaN.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from ._lib import SRMI_ERR_ARG, SRMI_NORM_AFFINE, call, load, ptr, stream_handle
+from .engine import Engine, NetSpec, downsample, engine_stream, upsample
+
+SUPPORTED_NORMS = ("lnorm", "lscale", "gnorm", "gscale")
+
+
+# ------------------------------------------------------------------ the plan
+def overlap_count(L: int, t: int, S: int) -> int:
+    """Number of tiles of the axis plan (L, t, S): ceil((L - t) / S) + 1."""
+    L, t, S = int(L), int(t), int(S)
+    if not 1 <= S <= t <= L:
+        raise ValueError(f"overlap plan needs 1 <= S <= t <= L, got L={L} t={t} S={S}")
+    return -((t - L) // S) + 1
+
+
+def overlap_plan(L: int, t: int, S: int) -> List[int]:
+    """Tile origins of the axis plan (L, t, S): min(i S, L - t) for i < n -- strictly
+    increasing, the first 0, the last L - t.  At S == t on a ragged axis (L % t != 0)
+    the shifted last tile overlaps its neighbour, and the blend averages the two there."""
+    n = overlap_count(L, t, S)
+    return [min(i * int(S), int(L) - int(t)) for i in range(n)]
+
+
+def blend_weight(p: int, t: int, S: int) -> int:
+    """Integer blend weight at tile-local position p of a tile t at stride S."""
+    if not 0 <= p < t:
+        raise ValueError(f"position {p} outside a tile of {t}")
+    return min(p + 1, t - p, t - S + 1)
+
+
+def lib_overlap_count(L: int, t: int, S: int) -> int:
+    """srmi_overlap_count of the library (host only): n, or ValueError where it returns
+    SRMI_ERR_ARG."""
+    n = load().srmi_overlap_count(int(L), int(t), int(S))
+    if n == SRMI_ERR_ARG:
+        raise ValueError(f"overlap plan needs 1 <= S <= t <= L, got L={L} t={t} S={S}")
+    return n
+
+
+# ---------------------------------------------------------------- the class
+class RegionSuperResolver:
+    def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw_lr: Tuple[int, int, int],
+                 tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
+                 task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
+                 device: Optional[torch.device] = None):
+        """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
+        runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
+        overlap).
+
+        norm / task: resolved as in TiledInference (task.norm, task.upsample_mode /
+        downsample_mode; the active ConfigContext's task when neither is given).  The
+        tile-local modes 'lnorm' and 'lscale' take their statistics from the LR tile
+        itself; the global modes 'gnorm' and 'gscale' take the dataset's global
+        constants from ``stats`` (srmi.norm.NormStats), one row per tile, as the AFFINE
+        mode.  'tnorm' and 'tscale' are refused: their statistics belong to the cells
+        of a floor grid, which overlapping tiles are not.  The output is ALWAYS
+        de-normalised (x * div + off, gnorm and gscale included): the purpose is a
+        physical field, not the reference's normalised mosaics.
+
+        An approximation, by construction: the model was trained on LR tiles that are
+        the downsampled HR tile NORMALISED BY THE HR TILE'S statistics; with no HR, the
+        LR tile's own statistics stand in for them (the mean of a bicubic 1/s of a
+        tile is close to the tile's, its spread somewhat smaller).
+
+        micro engines on their own streams share the tiles as TiledInference's do;
+        each runs its share in equal chunks of at most max_batch tiles (the forward
+        computes every tile alone, so neither changes a bit of the result).  An engine's
+        workspace grows with its chunk, and it refuses a chunk whose largest activation
+        map reaches 4 GiB (about 900 tiles of 48 x 48 at scale 4): lower max_batch for
+        larger tiles.  One chunk per engine is fastest (the inference RCAB runs one
+        workgroup per tile, so every chunk ends in a partly filled round of the engine's
+        CUs: 1024^2 LR at overlap 8 lost 2 % to chunks of 169).  graph: capture the
+        whole sequence in a HIP graph and replay it per region (bit-identical).
+        Multi-rank mode is not offered.  set_params as in TiledInference."""
+        if task is None:  # the active srmi ConfigContext's task section, if any
+            from . import config as _config
+            task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
+        from .config import interp_mode
+        from .norm import MODES, check_norm, norm_type
+        self.norm = check_norm(norm) if norm is not None else norm_type(task)
+        if self.norm not in SUPPORTED_NORMS:
+            raise ValueError(f"norm {self.norm!r}: its statistics belong to floor-grid cells; overlapping tiles take "
+                             f"one of {SUPPORTED_NORMS}")
+        self.norm_mode = MODES[self.norm]
+        if self.norm_mode == SRMI_NORM_AFFINE and stats is None:
+            raise ValueError(f"norm {self.norm!r} needs the dataset statistics (stats=NormStats)")
+        self.dmode, self.umode = interp_mode(task, True), interp_mode(task, False)
+        self.spec = spec
+        self.device = device or params.device
+        C, h, w = (int(v) for v in region_chw_lr)
+        if C != spec.nchannels_in or spec.nchannels_in != spec.nchannels_out:
+            raise ValueError("region channels must equal the model's input/output channels")
+        ty, tx = (int(v) for v in tile_lr)
+        ry, rx = (int(v) for v in overlap)
+        if ty < 1 or tx < 1 or h < ty or w < tx:
+            raise ValueError(f"region {(h, w)} smaller than one tile {(ty, tx)}")
+        if not (0 <= ry <= ty // 2 and 0 <= rx <= tx // 2):
+            raise ValueError(f"overlap {(ry, rx)} outside 0 .. tile // 2 = {(ty // 2, tx // 2)}")
+        s = spec.scale
+        self.C, self.h, self.w, self.ty, self.tx, self.s = C, h, w, ty, tx, s
+        self.sy, self.sx = ty - ry, tx - rx
+        self.ny, self.nx = overlap_count(h, ty, self.sy), overlap_count(w, tx, self.sx)
+        n = self.n = self.ny * self.nx
+        self.params = params
+        d = self.device
+        f32 = dict(dtype=torch.float32, device=d)
+        self.region = torch.empty((C, h, w), **f32)
+        self.tiles = torch.empty((n, C, ty, tx), **f32)
+        self.off = torch.empty((n, C), **f32)
+        self.div = torch.empty((n, C), **f32)
+        if self.norm_mode == SRMI_NORM_AFFINE:
+            # filled once, before any capture: the cut reads them, the blend undoes them
+            off, div = stats.offsets(self.norm, (0, n))
+            if tuple(off.shape) != (n, C):
+                raise ValueError(f"stats hold {tuple(off.shape[1:])} channels, the region has {C}")
+            self.off.copy_(off)
+            self.div.copy_(div)
+        self.bad = torch.zeros(n, dtype=torch.int32, device=d)
+        self.sr = torch.empty((n, C, ty * s, tx * s), **f32)
+        self.images = {"input": self.region, "interpolated": torch.empty((C, h * s, w * s), **f32),
+                       "model": torch.empty((C, h * s, w * s), **f32)}
+        if micro is None:
+            micro = 2 if n >= 32 else 1
+        self.micro = max(1, min(int(micro), n))
+        per = (n + self.micro - 1) // self.micro
+        self.split = [max(1, min(per, n - k * per)) for k in range(self.micro)]
+        self.max_batch = max(1, int(max_batch))
+        budget = 256 // self.micro if self.micro > 1 else 0
+        # an engine's share in the fewest chunks max_batch allows, of equal size
+        self.engs = [Engine(spec, -(-m // -(-m // self.max_batch)), (ty, tx), train=False, device=d, cu_budget=budget)
+                     for m in self.split]
+        self.eng = self.engs[0]
+        for e in self.engs:
+            e.pack(params)
+        self.streams = [None] + [engine_stream(d) for _ in range(self.micro - 1)]
+        self.ev_fork = torch.cuda.Event()
+        self.ev_join = [torch.cuda.Event() for _ in range(self.micro - 1)]
+        self.loss_m = torch.zeros(4, **f32)
+        self.loss_i = torch.zeros(4, **f32)
+        self._graph = None
+        self._use_graph = bool(graph) and self.device.type == "cuda"
+
+    # ---------------------------------------------------------------- pieces
+    def _cut(self):
+        call("srmi_region_to_tiles_overlap", ptr(self.region), self.C, self.h, self.w, self.ty, self.tx, self.sy,
+             self.sx, self.norm_mode, ptr(self.off), ptr(self.div), ptr(self.tiles), ptr(self.off), ptr(self.div),
+             ptr(self.bad), stream_handle())
+
+    def _forward(self):
+        main = torch.cuda.current_stream(self.device)
+        self.ev_fork.record(main)
+        for sk in self.streams[1:]:
+            sk.wait_event(self.ev_fork)
+        a = 0
+        for k, e in enumerate(self.engs):
+            b = min(self.n, a + self.split[k])
+            for c0 in range(a, b, e.batch):
+                c1 = min(b, c0 + e.batch)
+                if self.streams[k] is None:
+                    e.forward(self.params, self.tiles[c0:c1], out=self.sr[c0:c1])
+                else:
+                    with torch.cuda.stream(self.streams[k]):
+                        e.forward(self.params, self.tiles[c0:c1], out=self.sr[c0:c1])
+            a = b
+        for sk, ev in zip(self.streams[1:], self.ev_join):
+            ev.record(sk)
+            main.wait_event(ev)
+
+    def _blend(self):
+        s = self.s
+        call("srmi_tiles_blend", ptr(self.sr), ptr(self.off), ptr(self.div), ptr(self.bad), self.C, self.ty * s,
+             self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.images["model"]), stream_handle())
+
+    def _run(self):
+        self._cut()
+        self._forward()
+        upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
+        self._blend()
+
+    def _capture(self):
+        self._run()  # warm-up outside capture (uploads engine tables)
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                self._run()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self._graph = g
+
+    # ------------------------------------------------------------------- API
+    def super_resolve(self, lr_region: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """lr_region [C, h, w] fp32 (device) -> {'input': the LR region, 'interpolated':
+        task.upsample_mode of the whole LR region (untiled) [C, s h, s w], 'model': the
+        blended model output [C, s h, s w], de-normalised}.  Device tensors, views of
+        this object's buffers: valid until the next region."""
+        if tuple(lr_region.shape) != (self.C, self.h, self.w):
+            raise ValueError(f"region shape {tuple(lr_region.shape)} != {(self.C, self.h, self.w)}")
+        self.region.copy_(lr_region)
+        if self._use_graph:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+        else:
+            self._run()
+        return self.images
+
+    def score(self, hr_region: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+        """A number for choosing ``overlap``: hr_region [C, s h, s w] is downsampled
+        whole by task.downsample_mode, super-resolved, and the whole-region RMSE of
+        'model' and of 'interpolated' against it returned as 1-element device tensors
+        (srmi_rmse_partial / _finalize): (images, {'model', 'interpolated'})."""
+        s = self.s
+        if tuple(hr_region.shape) != (self.C, self.h * s, self.w * s):
+            raise ValueError(f"region shape {tuple(hr_region.shape)} != {(self.C, self.h * s, self.w * s)}")
+        hr = hr_region.contiguous()
+        images = self.super_resolve(downsample(hr[None], s, mode=self.dmode)[0])
+        for name, l4 in (("model", self.loss_m), ("interpolated", self.loss_i)):
+            self.eng.rmse_partial(images[name], hr, l4, float(hr.numel()))
+            Engine.rmse_finalize(l4)
+        return images, {"model": self.loss_m[3:4], "interpolated": self.loss_i[3:4]}
+
+    def set_params(self, params: torch.Tensor) -> None:
+        """Load new weights: copied into the parameter buffer the engines (and the
+        captured graph) read, filter packs rebuilt."""
+        self.params.copy_(params)
+        for e in self.engs:
+            e.pack(self.params)
