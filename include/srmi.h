@@ -45,6 +45,12 @@
  *                                   reference has no overlapped form: its tiles are the
  *                                   disjoint floor grid and its mosaic a concatenation.
  *                                   An extension, not a parity item.
+ *   srmi_region_to_tiles_overlap_masked,
+ *   srmi_tiles_blend_masked,
+ *   srmi_rmse_partial_masked     -> the three above and the RMSE for regions with land
+ *                                   (NaN): masked statistics, a flood fill, a re-masking
+ *                                   blend, a masked score.  No reference counterpart:
+ *                                   the reference drops every tile that touches land.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -421,6 +427,50 @@ int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int t
  * (SRMI_ERR_SHAPE); a plan out of range or a missing buffer: SRMI_ERR_ARG. */
 int srmi_tiles_blend(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty, int Tx,
                      int Sy, int Sx, int Ho, int Wo, float* out, void* stream);
+
+/* ---- land-aware forms (no reference counterpart) ------------------------ */
+/* srmi_region_to_tiles_overlap for regions with land: the same plan, tile order, modes
+ * and off / div / off_out / div_out, plus min_wet >= 1 and nwet [ny*nx][C] (optional).
+ * Per tile k and channel c, with "wet" = the finite pixels of the ty x tx plane:
+ *   nwet[k][c] = number of wet pixels; bad[k] = 1 iff some channel of the tile has
+ *   nwet < min_wet (an all-land tile is always bad); a bad tile's planes are 0.0f (it
+ *   still rides through the forward, and the blend never reads it).
+ *   Statistics over the wet pixels only.  LNORM: mean and 2-pass variance (ddof 0, / nwet)
+ *   as fp64 fixed-order block reductions, off_out = (float)mean, div_out = (float)std,
+ *   x' = (float)(((double)x - mean) * (1 / std)) -- deliberately NOT the fp32 two-pass
+ *   of the unmasked LNORM cut (srmi_region_to_tiles), so LNORM results differ from it in
+ *   the last bits even without land.  LSCALE (min, max over the wet pixels) and AFFINE:
+ *   the arithmetic of srmi_region_to_tiles_norm; on a region with no non-finite value
+ *   tiles, off_out, div_out and bad are srmi_region_to_tiles_overlap's bit for bit.
+ *   Zero spread gives the IEEE result.
+ *   Dry pixels are flood-filled in normalised space: pass j = 1, 2, ... gives every pixel
+ *   not yet filled that has a filled 8-neighbour inside the tile the mean of those
+ *   neighbours -- fp32 adds from 0.0f in the order (dy, dx) = (-1,-1) (-1,0) (-1,1) (0,-1)
+ *   (0,1) (1,-1) (1,0) (1,1), then one fp32 multiply by fp32(1 / count).  Passes are
+ *   simultaneous (a pass reads only what was filled before it); at most max(ty, tx) - 1.
+ * One workgroup per (channel, tile); the plane lives in LDS with a 16-bit pass stamp per
+ * pixel, 6 bytes a pixel: ty * tx <= 25600 (160 x 160), else SRMI_ERR_SHAPE, as for
+ * ny*nx > 65535.  The trip count is decided on the device: no host read, capturable.
+ * min_wet < 1, a plan or mode out of range, a missing buffer: SRMI_ERR_ARG. */
+int srmi_region_to_tiles_overlap_masked(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
+                                        int mode, const float* off, const float* div, float* tiles, float* off_out,
+                                        float* div_out, int* bad, int min_wet, int* nwet, void* stream);
+/* srmi_tiles_blend that puts the land back: output pixel (c, Y, X) is the canonical NaN
+ * where mask_src[c][Y / scale][X / scale] (mask_src [C][Ho / scale][Wo / scale], the LR
+ * region itself) is not finite -- decided before any tile is read -- and exactly
+ * srmi_tiles_blend's value elsewhere (the same kernel, a compile-time flag).  The quad
+ * form additionally needs scale % 4 == 0.  mask_src NULL, scale < 1, or Ho, Wo not
+ * multiples of scale: SRMI_ERR_ARG; otherwise as srmi_tiles_blend. */
+int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty,
+                            int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                            void* stream);
+/* srmi_rmse_partial over the elements where pred and target are both finite: loss4[0] =
+ * S = sum (p - t)^2, loss4[1] = their count, both written by the device (two stages,
+ * fixed order, fp64 differences and partials, no atomics); srmi_rmse_finalize then works
+ * unchanged.  count == 0 gives the IEEE result: loss4[3] = sqrt(0 / 0) = NaN.  The count
+ * is stored as a float: exact up to 2^24 elements. */
+int srmi_rmse_partial_masked(srmi_engine* e, const float* pred, const float* target, size_t n, float* loss4,
+                             void* stream);
 
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)

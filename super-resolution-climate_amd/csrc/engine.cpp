@@ -1329,6 +1329,13 @@ int srmi_rmse_partial(srmi_engine* e, const float* pred, const float* target, si
   return sqerr_finish_launch(e->lpart, e->lpart_n, count_global, loss4, S_(stream));
 }
 
+int srmi_rmse_partial_masked(srmi_engine* e, const float* pred, const float* target, size_t n, float* loss4,
+                             void* stream) {
+  if (!e || !pred || !target || !loss4) return SRMI_ERR_ARG;
+  // the engine's partial buffer (lpart_n floats, 256-byte aligned) as {S, count} doubles of lpart_n / 4 blocks
+  return sqerr_masked_launch(pred, target, n, reinterpret_cast<double*>(e->lpart), e->lpart_n / 4, loss4, S_(stream));
+}
+
 int srmi_rmse_finalize(float* loss4, void* stream) {
   if (!loss4) return SRMI_ERR_ARG;
   return loss_finalize_launch(loss4, LOSS_RMSE, S_(stream));
@@ -1577,6 +1584,19 @@ int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int t
 int srmi_tiles_blend(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty, int Tx,
                      int Sy, int Sx, int Ho, int Wo, float* out, void* stream) {
   return tiles_blend_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, out, S_(stream));
+}
+
+int srmi_region_to_tiles_overlap_masked(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
+                                        int mode, const float* off, const float* div, float* tiles, float* off_out,
+                                        float* div_out, int* bad, int min_wet, int* nwet, void* stream) {
+  return region_to_tiles_overlap_masked_launch(region, C, H, W, ty, tx, sy, sx, mode, off, div, tiles, off_out,
+                                               div_out, bad, min_wet, nwet, S_(stream));
+}
+
+int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty,
+                            int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                            void* stream) {
+  return tiles_blend_masked_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, S_(stream));
 }
 
 int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {

@@ -891,6 +891,85 @@ int sqerr_finish_launch(const float* partial, int nblk, double count, float* los
   return 0;
 }
 
+// The masked form (srmi_rmse_partial_masked; no reference counterpart: l2loss knows no
+// mask): the sum of (y - t)^2 and the COUNT over the elements where both are finite, a
+// field with land against a truth with land.  Two stages in a fixed order like the pair
+// above, no atomics; the difference, the per-thread sums and the block partials
+// {S, count} are fp64 (a count is exact there up to 2^53).  partial: [2][nblk] doubles.
+__global__ void __launch_bounds__(256) sqerr_masked_partial_kernel(const float* __restrict__ y,
+                                                                   const float* __restrict__ t, size_t n,
+                                                                   double* __restrict__ partial) {
+  __shared__ double red[8];
+  double s = 0.0, k = 0.0;
+  auto one = [&](float a, float b) __attribute__((always_inline)) {
+    if (isfinite(a) && isfinite(b)) {
+      const double d = (double)a - (double)b;
+      s += d * d;
+      k += 1.0;
+    }
+  };
+  const bool vec = (((uintptr_t)y | (uintptr_t)t) & 15) == 0;
+  const size_t n4 = vec ? n / 4 : 0;
+  const float4* y4 = reinterpret_cast<const float4*>(y);
+  const float4* t4 = reinterpret_cast<const float4*>(t);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float4 a = y4[i], b = t4[i];
+    one(a.x, b.x);
+    one(a.y, b.y);
+    one(a.z, b.z);
+    one(a.w, b.w);
+  }
+  for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) one(y[i], t[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, 64);
+    k += __shfl_xor(k, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = s;
+    red[4 + (threadIdx.x >> 6)] = k;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    partial[gridDim.x + blockIdx.x] = (red[4] + red[5]) + (red[6] + red[7]);
+  }
+}
+
+// loss[0] = S, loss[1] = count, both from the device (count == 0: srmi_rmse_finalize
+// then gives sqrt(0 / 0) = NaN, the IEEE result)
+__global__ void __launch_bounds__(256) sqerr_masked_finish_kernel(const double* __restrict__ partial, int nblk,
+                                                                  float* loss) {
+  __shared__ double red[2][256];
+  double s = 0.0, k = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) {
+    s += partial[i];
+    k += partial[nblk + i];
+  }
+  red[0][threadIdx.x] = s;
+  red[1][threadIdx.x] = k;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + o];
+      red[1][threadIdx.x] += red[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = (float)red[0][0];
+    loss[1] = (float)red[1][0];
+  }
+}
+
+int sqerr_masked_launch(const float* y, const float* t, size_t n, double* partial, int nblk, float* loss,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(sqerr_masked_partial_kernel, dim3(nblk), dim3(256), 0, st, y, t, n, partial);
+  hipLaunchKernelGGL(sqerr_masked_finish_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
 // Charbonnier loss of ModelTrainer.charbonnier (sres/controller/dual_trainer.py:196-198):
 // L = mean(sqrt(d^2 + eps)), d = y - t; partial sums like sqerr_partial_kernel and,
 // when dy != NULL, the elementwise gradient dL/dy = d / sqrt(d^2 + eps) / count.

@@ -196,6 +196,10 @@ int interp_launch(const float* x, int N, int C, int H, int W, int Ho, int Wo, fl
 // loss[0] = sum (y-t)^2 (this rank), loss[1] = element count (global after all-reduce)
 int sqerr_partial_launch(const float* y, const float* t, size_t n, float* partial, int nblk, hipStream_t st);
 int sqerr_finish_launch(const float* partial, int nblk, double count, float* loss, hipStream_t st);
+// the same over the elements where y and t are both finite; loss[1] = their count.
+// partial: 2 * nblk doubles
+int sqerr_masked_launch(const float* y, const float* t, size_t n, double* partial, int nblk, float* loss,
+                        hipStream_t st);
 enum LossKind { LOSS_RMSE = 0, LOSS_MEAN = 1 };
 int loss_finalize_launch(float* loss, int kind, hipStream_t st);
 int loss_combine_launch(float* loss, const float* parts, int nparts, int kind, hipStream_t st);
@@ -289,6 +293,13 @@ int region_to_tiles_overlap_launch(const float* region, int C, int H, int W, int
                                    int* bad, hipStream_t st);
 int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
                        int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st);
+// the land-aware forms: masked cut with a fill, re-masking blend (tiles.hip)
+int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
+                                          int mode, const float* off, const float* dv, float* tiles, float* off_out,
+                                          float* div_out, int* bad, int min_wet, int* nwet, hipStream_t st);
+int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
+                              int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                              hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

@@ -683,14 +683,28 @@ __device__ __forceinline__ int overlap_weight(int q, int t, int R) { return min(
 // bit for bit).  kV == 4: Tx, Sx, Wo multiples of 4 put every tile edge on a quad
 // boundary, so the quad has one cover and its tile rows are 16-byte aligned.
 // grid (ceil(Wo / kV / 256), Ho, C)
-template <int kV>
+// kMask (srmi_tiles_blend_masked): a pixel whose parent mask_src[c][Y / scale][X / scale]
+// is not finite is the canonical NaN, decided before any tile is read; every other pixel
+// runs the code below unchanged.  kV == 4 there also needs scale % 4 == 0: the quad then
+// has one parent.
+template <int kV, bool kMask>
 __global__ void __launch_bounds__(256) tiles_blend_kernel(const float* __restrict__ tiles,
                                                           const float* __restrict__ off,
                                                           const float* __restrict__ dv, const int* __restrict__ bad,
                                                           int C, int Ty, int Tx, int Sy, int Sx, int ny, int nx,
-                                                          int Ho, int Wo, float* __restrict__ out) {
+                                                          int Ho, int Wo, const float* __restrict__ mask_src,
+                                                          int scale, float* __restrict__ out) {
   const int X = (blockIdx.x * 256 + threadIdx.x) * kV, Y = blockIdx.y, c = blockIdx.z;
   if (X >= Wo) return;
+  if constexpr (kMask) {
+    if (!isfinite(mask_src[((size_t)c * (Ho / scale) + Y / scale) * (Wo / scale) + X / scale])) {
+      const float nan = __int_as_float(0x7fc00000);
+      float* dst = out + ((size_t)c * Ho + Y) * Wo + X;
+      if constexpr (kV == 4) *reinterpret_cast<float4*>(dst) = make_float4(nan, nan, nan, nan);
+      else dst[0] = nan;
+      return;
+    }
+  }
   const int Ry = Ty - Sy, Rx = Tx - Sx;
   int ylo, yhi, xlo, xhi;
   overlap_cover(Y, Ho, Ty, Sy, ny, ylo, yhi);
@@ -743,8 +757,10 @@ __global__ void __launch_bounds__(256) tiles_blend_kernel(const float* __restric
   else dst[0] = r[0];
 }
 
-int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
-                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st) {
+// mask_src == NULL: srmi_tiles_blend; else srmi_tiles_blend_masked (scale >= 1 divides Ho, Wo)
+static int tiles_blend_any_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
+                                  int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                                  hipStream_t st) {
   if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.z
   const int ny = overlap_count(Ho, Ty, Sy), nx = overlap_count(Wo, Tx, Sx);
   if (ny < 0 || nx < 0) return SRMI_ERR_ARG;
@@ -754,15 +770,32 @@ int tiles_blend_launch(const float* tiles, const float* off, const float* dv, co
   if (Ho > 65535 || (long long)ny * nx > 0x7fffffffLL || wy * wx > 0x7fffffffLL) return SRMI_ERR_SHAPE;
   if (!tiles || !out || (off && !dv)) return SRMI_ERR_ARG;
   const bool vec = Tx % 4 == 0 && Sx % 4 == 0 && Wo % 4 == 0 && ((uintptr_t)tiles & 15) == 0 &&
-                   ((uintptr_t)out & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(tiles_blend_kernel<4>, dim3((Wo / 4 + 255) / 256, Ho, C), dim3(256), 0, st, tiles, off, dv,
-                       bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, out);
-  else
-    hipLaunchKernelGGL(tiles_blend_kernel<1>, dim3((Wo + 255) / 256, Ho, C), dim3(256), 0, st, tiles, off, dv, bad, C,
-                       Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, out);
+                   ((uintptr_t)out & 15) == 0 && (!mask_src || scale % 4 == 0);
+#define SRMI_BLEND(V, MASK)                                                                                          \
+  hipLaunchKernelGGL((tiles_blend_kernel<V, MASK>), dim3((Wo / V + 255) / 256, Ho, C), dim3(256), 0, st, tiles, off, \
+                     dv, bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, mask_src, scale, out)
+  if (mask_src) {
+    if (vec) SRMI_BLEND(4, true);
+    else SRMI_BLEND(1, true);
+  } else {
+    if (vec) SRMI_BLEND(4, false);
+    else SRMI_BLEND(1, false);
+  }
+#undef SRMI_BLEND
   SRMI_CHECK_LAUNCH();
   return 0;
+}
+
+int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
+                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st) {
+  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, nullptr, 1, out, st);
+}
+
+int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
+                              int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                              hipStream_t st) {
+  if (!mask_src || scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale) return SRMI_ERR_ARG;
+  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, st);
 }
 
 // ------------------------------------------------------ dataset tile statistics
@@ -926,6 +959,235 @@ int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes
                        (double)ntimes, tstats);
   if (gstats)
     hipLaunchKernelGGL(tile_stats_global_kernel, dim3(C), dim3(1024), 0, st, acc, n, C, (double)ntimes, gstats);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// --------------------------------------------------- land-aware overlapped cut
+// No reference counterpart: get_tiles (raw.py:216-233) drops every tile that holds a
+// non-finite value, and so does region_to_tiles_overlap above.  Here the non-finite
+// ("dry": land, ice) pixels of a tile are masked out of its statistics and filled from
+// the wet ones, so a coastal tile rides through the forward like any other; the masked
+// blend puts the NaN back.  One workgroup (1024 threads) per (channel, tile), grid
+// (C, ny * nx) as the unmasked cut.  The plane is read from HBM once into LDS (values
+// fp32 + a 16-bit pass stamp per pixel: 6 bytes a pixel, 54 KiB at 96 x 96; planes of more
+// than kLandMaxPix pixels are refused), normalised there, filled there, written once.
+//
+// Statistics over the wet pixels only.  LNORM: mean and the 2-pass variance (ddof 0, over
+// nwet) are fp64 fixed-order block reductions (block_sum_f64, as tile_stats and
+// batch_prep), x - mean is formed in fp64 and multiplied by the fp64 1 / std --
+// deliberately NOT the fp32 two-pass of region_to_tiles_kernel: a coastal tile's few wet
+// pixels sit far from 0, where an fp32 mean costs the most.  LSCALE / AFFINE: the
+// arithmetic of region_to_tiles_norm_kernel, so an all-finite region gives its bits.
+//
+// Fill, in normalised space (the neighbour averaging of ocean regridding tools): pass
+// j = 1, 2, ... gives every pixel not filled before pass j that has a filled 8-neighbour
+// inside the tile the mean of those neighbours -- fp32 adds from 0.0f in the order
+// (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1), one fp32 multiply by
+// kLandRecip[count - 1] -- and stamps it j.  A neighbour counts iff its stamp < j, so the
+// update is Jacobi though it runs in place: a pixel stamped j in this pass is ignored by
+// the others whether they see the stamp before or after the store.  One barrier per pass
+// (__syncthreads_count, which is also the termination test: nothing unfilled); with
+// nwet >= 1 at most max(ty, tx) - 1 passes.  No host read: the sequence stays capturable.
+//
+// The bad flag is per TILE (some channel has nwet < min_wet) but a workgroup owns one
+// channel, so each counts the finite pixels of the tile's other channels too (L2 reads,
+// nothing for C == 1); channel 0's workgroup stores the flag, so this cut needs neither
+// the memset nor the atomicOr of the unmasked one.  A bad tile's planes are 0.0f.
+constexpr int kLandThreads = 1024;
+constexpr int kLandMaxPix = 25600;  // 6 bytes a pixel in 150 KiB of LDS (160 x 160)
+constexpr unsigned short kLandDry = 0xffffu;
+__constant__ float kLandRecip[8] = {1.f, 1.f / 2.f, 1.f / 3.f, 1.f / 4.f, 1.f / 5.f, 1.f / 6.f, 1.f / 7.f, 1.f / 8.f};
+
+__device__ __forceinline__ int block_sum_i32(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int s = 0;
+#pragma unroll
+  for (int i = 0; i < kLandThreads / 64; ++i) s += red[i];
+  __syncthreads();
+  return s;
+}
+
+template <int kMode, bool kVec>
+__global__ void __launch_bounds__(kLandThreads) region_to_tiles_masked_kernel(
+    const float* __restrict__ region, int C, int H, int W, int ty, int tx, int gx, int sy, int sx, int min_wet,
+    const float* __restrict__ off, const float* __restrict__ dv, float* __restrict__ tiles,
+    float* __restrict__ off_out, float* __restrict__ div_out, int* __restrict__ bad, int* __restrict__ nwet) {
+  extern __shared__ float tile[];  // val[ty * tx], then the stamps
+  __shared__ double red[kLandThreads / 64];
+  __shared__ float redf[2 * kLandThreads / 64];
+  __shared__ int redi[kLandThreads / 64];
+  const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+  const int y0 = min((t / gx) * sy, H - ty), x0 = min((t % gx) * sx, W - tx);
+  const int n = ty * tx;
+  float* val = tile;
+  unsigned short* stamp = reinterpret_cast<unsigned short*>(tile + n);
+  const size_t p = (size_t)t * C + c;
+  const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
+  // 1. the plane -> LDS, raw; stamp 0 = wet
+  if (kVec) {
+    const int tx4 = tx >> 2, n4 = ty * tx4;
+    for (int i = tid; i < n4; i += kLandThreads) {
+      const int r = i / tx4, q = i - r * tx4;
+      const float4 v = *reinterpret_cast<const float4*>(src + (size_t)r * W + 4 * q);
+      const int o = r * tx + 4 * q;
+      val[o] = v.x; val[o + 1] = v.y; val[o + 2] = v.z; val[o + 3] = v.w;
+      stamp[o] = isfinite(v.x) ? 0 : kLandDry;
+      stamp[o + 1] = isfinite(v.y) ? 0 : kLandDry;
+      stamp[o + 2] = isfinite(v.z) ? 0 : kLandDry;
+      stamp[o + 3] = isfinite(v.w) ? 0 : kLandDry;
+    }
+  } else {
+    for (int i = tid; i < n; i += kLandThreads) {
+      const float a = src[(size_t)(i / tx) * W + (i % tx)];
+      val[i] = a;
+      stamp[i] = isfinite(a) ? 0 : kLandDry;
+    }
+  }
+  // 2. is the tile bad?  the wet count of every channel of it
+  int isbad = 0;
+  for (int cc = 0; cc < C; ++cc) {
+    if (cc == c) continue;
+    const float* s2 = region + (size_t)cc * H * W + (size_t)y0 * W + x0;
+    int k = 0;
+    for (int i = tid; i < n; i += kLandThreads) k += isfinite(s2[(size_t)(i / tx) * W + (i % tx)]);
+    isbad |= block_sum_i32(k, redi) < min_wet;
+  }
+  __syncthreads();  // the LDS plane is complete
+  // 3. statistics over the wet pixels; from here a thread owns the pixels tid, tid + 1024, ...
+  int k = 0;
+  double s = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = tid; i < n; i += kLandThreads) {
+    if (stamp[i] == 0) {
+      const float a = val[i];
+      ++k;
+      if (kMode == SRMI_NORM_LNORM) s += (double)a;
+      if (kMode == SRMI_NORM_LSCALE) {
+        mn = fminf(mn, a);
+        mx = fmaxf(mx, a);
+      }
+    }
+  }
+  const int nw = block_sum_i32(k, redi);
+  isbad |= nw < min_wet;
+  double o, inv, sd = 0.0;
+  if (kMode == SRMI_NORM_LNORM) {
+    o = block_sum_f64<kLandThreads>(s, red) / (double)nw;
+    double q = 0.0;
+    for (int i = tid; i < n; i += kLandThreads) {
+      if (stamp[i] == 0) {
+        const double d = (double)val[i] - o;
+        q += d * d;
+      }
+    }
+    sd = sqrt(block_sum_f64<kLandThreads>(q, red) / (double)nw);
+    inv = 1.0 / sd;
+  } else if (kMode == SRMI_NORM_LSCALE) {
+    block_minmax<kLandThreads>(mn, mx, redf);
+    o = (double)mn;
+    inv = 1.0 / ((double)mx - (double)mn);
+  } else {
+    o = (double)off[p];
+    inv = 1.0 / (double)dv[p];
+  }
+  if (tid == 0) {
+    if (nwet) nwet[p] = nw;
+    if (kMode == SRMI_NORM_LNORM) {
+      off_out[p] = (float)o;
+      div_out[p] = (float)sd;
+    } else if (kMode == SRMI_NORM_LSCALE) {
+      if (off_out) off_out[p] = mn;
+      if (div_out) div_out[p] = mx - mn;
+    }
+    // every workgroup of the tile has counted all its channels and holds the same flag:
+    // channel 0's stores it -- no memset before the launch, no atomic
+    if (bad && c == 0) bad[t] = isbad;
+  }
+  float* dst = tiles + p * n;
+  if (isbad) {  // (uniform over the block) finite planes for the forward; the blend never reads them
+    for (int i = tid; i < n; i += kLandThreads) dst[i] = 0.f;
+    return;
+  }
+  // 4. normalise the wet pixels in place
+  for (int i = tid; i < n; i += kLandThreads)
+    if (stamp[i] == 0) val[i] = (float)(((double)val[i] - o) * inv);
+  __syncthreads();
+  // 5. flood fill; not bad => nwet >= min_wet >= 1, so it ends within max(ty, tx) - 1 passes
+  const int jmax = max(ty, tx);
+  for (int j = 1; j < jmax; ++j) {
+    int left = 0;
+    for (int i = tid; i < n; i += kLandThreads) {
+      if (stamp[i] != kLandDry) continue;
+      const int y = i / tx, x = i - y * tx;
+      float acc = 0.f;
+      int cnt = 0;
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+          if (dy == 0 && dx == 0) continue;
+          const int yy = y + dy, xx = x + dx;
+          if (yy < 0 || yy >= ty || xx < 0 || xx >= tx) continue;
+          const int q = yy * tx + xx;
+          if ((int)stamp[q] < j) {
+            acc += val[q];
+            ++cnt;
+          }
+        }
+      }
+      if (cnt) {
+        val[i] = acc * kLandRecip[cnt - 1];
+        stamp[i] = (unsigned short)j;
+      } else {
+        left = 1;
+      }
+    }
+    if (__syncthreads_count(left) == 0) break;
+  }
+  // 6. the tile, once
+  if (kVec) {
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    for (int i = tid; i < n / 4; i += kLandThreads)
+      d4[i] = make_float4(val[4 * i], val[4 * i + 1], val[4 * i + 2], val[4 * i + 3]);
+  } else {
+    for (int i = tid; i < n; i += kLandThreads) dst[i] = val[i];
+  }
+}
+
+int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
+                                          int mode, const float* off, const float* dv, float* tiles, float* off_out,
+                                          float* div_out, int* bad, int min_wet, int* nwet, hipStream_t st) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || C > 65535 || min_wet < 1) return SRMI_ERR_ARG;  // grid.x
+  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
+  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
+      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
+    return SRMI_ERR_ARG;
+  if ((long long)ty * tx > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
+  const bool vec = tx % 4 == 0 && W % 4 == 0 && sx % 4 == 0 && ((uintptr_t)region & 15) == 0 &&
+                   ((uintptr_t)tiles & 15) == 0;
+  const size_t lds = (size_t)ty * tx * (sizeof(float) + sizeof(unsigned short));
+  const dim3 grid(C, gy * gx), block(kLandThreads);
+#define SRMI_R2T_MASKED(MODE, VEC)                                                                                 \
+  hipLaunchKernelGGL((region_to_tiles_masked_kernel<MODE, VEC>), grid, block, lds, st, region, C, H, W, ty, tx, gx, \
+                     sy, sx, min_wet, off, dv, tiles, off_out, div_out, bad, nwet)
+  if (mode == SRMI_NORM_LNORM) {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LNORM, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_LNORM, false);
+  } else if (mode == SRMI_NORM_LSCALE) {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LSCALE, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_LSCALE, false);
+  } else {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_AFFINE, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_AFFINE, false);
+  }
+#undef SRMI_R2T_MASKED
   SRMI_CHECK_LAUNCH();
   return 0;
 }

@@ -120,6 +120,11 @@ _SIGS = {
     "srmi_region_to_tiles_overlap": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P,
                                       P, P, P, P], C.c_int),
     "srmi_tiles_blend": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
+    "srmi_region_to_tiles_overlap_masked": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             P, P, P, P, P, P, C.c_int, P, P], C.c_int),
+    "srmi_tiles_blend_masked": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int,
+                                 P, P], C.c_int),
+    "srmi_rmse_partial_masked": ([P, P, P, C.c_size_t, P, P], C.c_int),
     "srmi_tile_stats": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, P, C.c_int, P], C.c_int),
     "srmi_tile_stats_finalize": ([P, C.c_longlong, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_llc_index_map_workspace": ([C.c_longlong, C.POINTER(C.c_size_t)], C.c_int),

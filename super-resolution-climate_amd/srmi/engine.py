@@ -250,6 +250,12 @@ class Engine:
         call("srmi_rmse_partial", self._h, ptr(pred), ptr(target), pred.numel(), float(count_global), ptr(loss4),
              stream_handle(stream))
 
+    def rmse_partial_masked(self, pred: torch.Tensor, target: torch.Tensor, loss4: torch.Tensor, stream=None):
+        """rmse_partial over the elements where pred and target are both finite; loss4[1] is
+        their count, written by the device (srmi_rmse_partial_masked)."""
+        call("srmi_rmse_partial_masked", self._h, ptr(pred), ptr(target), pred.numel(), ptr(loss4),
+             stream_handle(stream))
+
     def charbonnier_partial(self, pred: torch.Tensor, target: torch.Tensor, loss4: torch.Tensor,
                             count_global: float, eps: float = 1e-6, dy: Optional[torch.Tensor] = None, stream=None):
         """ModelTrainer.charbonnier (dual_trainer.py:196-198) partial sums (+ dL/dpred into dy)."""

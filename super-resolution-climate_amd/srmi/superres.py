@@ -32,12 +32,34 @@ linear ramp that never reaches zero.  With ``R = 0`` every weight is 1, so a rag
 at ``R = 0`` AVERAGES the shifted last tile with its neighbour where the two overlap
 (and a region the tile divides is the plain mosaic).
 
-Bad tiles: a tile holding a non-finite value is flagged by the cut, rides through the
-forward, and is ignored by the blend (its values are never read).  A pixel whose
-covering tiles are all bad is NaN.
+Bad tiles: by default (``land=False``) a tile holding a non-finite value is flagged by
+the cut, rides through the forward, and is ignored by the blend (its values are never
+read).  A pixel whose covering tiles are all bad is NaN -- so one land pixel blanks up
+to a whole tile of ocean around it.
+
+Land (``land=True``)
+--------------------
+For regions whose land, ice or missing data is NaN (srmi.llc writes land as NaN).  The
+cut is ``srmi_region_to_tiles_overlap_masked``: a tile's statistics are taken over its
+finite ("wet") pixels only, its dry pixels are flood-filled in normalised space from
+the wet ones (pass by pass, the mean of the already filled 8-neighbours), and it is bad
+only when some channel has fewer than ``min_wet`` (a fraction of the tile plane) wet
+pixels; a bad tile is all zeros and, as above, ignored by the blend.  The blend is
+``srmi_tiles_blend_masked``: every HR pixel whose LR parent is not finite is NaN again,
+every other pixel is the plain blend of the non-bad tiles covering it.  So the holes of
+the result are the land itself (plus the pixels all of whose tiles are bad), not the
+tiles around it.  'interpolated' becomes the TILED baseline: the upsample of the filled,
+normalised LR tiles, blended and re-masked the same way (upsampling is affine-invariant,
+so the blend's x * div + off de-normalises it) -- the whole-region upsample of a NaN
+field would lose a strip of ocean along every coast.  ``score`` takes an HR truth with
+NaN and counts only the pixels where both sides are finite
+(``srmi_rmse_partial_masked``).  No host synchronisation anywhere: the fill's trip count
+is decided on the device, so ``graph=True`` works and one captured graph serves regions
+with different coasts.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -86,7 +108,7 @@ class RegionSuperResolver:
     def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw_lr: Tuple[int, int, int],
                  tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
                  task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25):
         """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
         runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
         overlap).
@@ -115,7 +137,12 @@ class RegionSuperResolver:
         workgroup per tile, so every chunk ends in a partly filled round of the engine's
         CUs: 1024^2 LR at overlap 8 lost 2 % to chunks of 169).  graph: capture the
         whole sequence in a HIP graph and replay it per region (bit-identical).
-        Multi-rank mode is not offered.  set_params as in TiledInference."""
+        Multi-rank mode is not offered.  set_params as in TiledInference.
+
+        land: the region may hold NaN (land); see the module docstring.  min_wet, in
+        (0, 1]: the share of a tile plane that must be wet in every channel for the tile
+        to be used (the ABI gets max(1, ceil(min_wet ty tx)) pixels).  land=False is the
+        object as it was, bit for bit."""
         if task is None:  # the active srmi ConfigContext's task section, if any
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
@@ -142,6 +169,11 @@ class RegionSuperResolver:
             raise ValueError(f"overlap {(ry, rx)} outside 0 .. tile // 2 = {(ty // 2, tx // 2)}")
         s = spec.scale
         self.C, self.h, self.w, self.ty, self.tx, self.s = C, h, w, ty, tx, s
+        self.land = bool(land)
+        if self.land:
+            if not 0.0 < float(min_wet) <= 1.0:
+                raise ValueError(f"min_wet {min_wet!r} outside (0, 1]")
+            self.min_wet = max(1, math.ceil(float(min_wet) * ty * tx))
         self.sy, self.sx = ty - ry, tx - rx
         self.ny, self.nx = overlap_count(h, ty, self.sy), overlap_count(w, tx, self.sx)
         n = self.n = self.ny * self.nx
@@ -163,6 +195,10 @@ class RegionSuperResolver:
         self.sr = torch.empty((n, C, ty * s, tx * s), **f32)
         self.images = {"input": self.region, "interpolated": torch.empty((C, h * s, w * s), **f32),
                        "model": torch.empty((C, h * s, w * s), **f32)}
+        if self.land:
+            self.nwet = torch.zeros((n, C), dtype=torch.int32, device=d)
+            self.up = torch.empty((n, C, ty * s, tx * s), **f32)  # the tiled baseline's tiles
+            self.images["nwet"] = self.nwet
         if micro is None:
             micro = 2 if n >= 32 else 1
         self.micro = max(1, min(int(micro), n))
@@ -186,6 +222,11 @@ class RegionSuperResolver:
 
     # ---------------------------------------------------------------- pieces
     def _cut(self):
+        if self.land:
+            call("srmi_region_to_tiles_overlap_masked", ptr(self.region), self.C, self.h, self.w, self.ty, self.tx,
+                 self.sy, self.sx, self.norm_mode, ptr(self.off), ptr(self.div), ptr(self.tiles), ptr(self.off),
+                 ptr(self.div), ptr(self.bad), self.min_wet, ptr(self.nwet), stream_handle())
+            return
         call("srmi_region_to_tiles_overlap", ptr(self.region), self.C, self.h, self.w, self.ty, self.tx, self.sy,
              self.sx, self.norm_mode, ptr(self.off), ptr(self.div), ptr(self.tiles), ptr(self.off), ptr(self.div),
              ptr(self.bad), stream_handle())
@@ -210,15 +251,28 @@ class RegionSuperResolver:
             ev.record(sk)
             main.wait_event(ev)
 
+    def _blend_masked(self, tiles: torch.Tensor, out: torch.Tensor):
+        s = self.s
+        call("srmi_tiles_blend_masked", ptr(tiles), ptr(self.off), ptr(self.div), ptr(self.bad), self.C, self.ty * s,
+             self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.region), s, ptr(out),
+             stream_handle())
+
     def _blend(self):
         s = self.s
+        if self.land:
+            self._blend_masked(self.sr, self.images["model"])
+            return
         call("srmi_tiles_blend", ptr(self.sr), ptr(self.off), ptr(self.div), ptr(self.bad), self.C, self.ty * s,
              self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.images["model"]), stream_handle())
 
     def _run(self):
         self._cut()
         self._forward()
-        upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
+        if self.land:  # the tiled baseline: every tile plane upsampled alone, blended like the model's
+            upsample(self.tiles, self.s, out=self.up, mode=self.umode)
+            self._blend_masked(self.up, self.images["interpolated"])
+        else:
+            upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
         self._blend()
 
     def _capture(self):
@@ -238,7 +292,11 @@ class RegionSuperResolver:
         """lr_region [C, h, w] fp32 (device) -> {'input': the LR region, 'interpolated':
         task.upsample_mode of the whole LR region (untiled) [C, s h, s w], 'model': the
         blended model output [C, s h, s w], de-normalised}.  Device tensors, views of
-        this object's buffers: valid until the next region."""
+        this object's buffers: valid until the next region.
+
+        land=True: lr_region may hold NaN; 'model' and 'interpolated' (then the tiled
+        baseline) are NaN exactly on the upsampled dry pixels and where every covering
+        tile is bad, and 'nwet' [n, C] int32 holds the wet count of every tile plane."""
         if tuple(lr_region.shape) != (self.C, self.h, self.w):
             raise ValueError(f"region shape {tuple(lr_region.shape)} != {(self.C, self.h, self.w)}")
         self.region.copy_(lr_region)
@@ -254,16 +312,27 @@ class RegionSuperResolver:
         """A number for choosing ``overlap``: hr_region [C, s h, s w] is downsampled
         whole by task.downsample_mode, super-resolved, and the whole-region RMSE of
         'model' and of 'interpolated' against it returned as 1-element device tensors
-        (srmi_rmse_partial / _finalize): (images, {'model', 'interpolated'})."""
+        (srmi_rmse_partial / _finalize): (images, {'model', 'interpolated'}).
+
+        land=True: hr_region may hold NaN (its downsample is then NaN wherever a tap
+        touches one); both losses are taken over the pixels where the image and
+        hr_region are both finite (srmi_rmse_partial_masked), and the dict gains
+        'count', that number of pixels for 'model' (no such pixel: the losses are NaN)."""
         s = self.s
         if tuple(hr_region.shape) != (self.C, self.h * s, self.w * s):
             raise ValueError(f"region shape {tuple(hr_region.shape)} != {(self.C, self.h * s, self.w * s)}")
         hr = hr_region.contiguous()
         images = self.super_resolve(downsample(hr[None], s, mode=self.dmode)[0])
         for name, l4 in (("model", self.loss_m), ("interpolated", self.loss_i)):
-            self.eng.rmse_partial(images[name], hr, l4, float(hr.numel()))
+            if self.land:
+                self.eng.rmse_partial_masked(images[name], hr, l4)
+            else:
+                self.eng.rmse_partial(images[name], hr, l4, float(hr.numel()))
             Engine.rmse_finalize(l4)
-        return images, {"model": self.loss_m[3:4], "interpolated": self.loss_i[3:4]}
+        losses = {"model": self.loss_m[3:4], "interpolated": self.loss_i[3:4]}
+        if self.land:
+            losses["count"] = self.loss_m[1:2]
+        return images, losses
 
     def set_params(self, params: torch.Tensor) -> None:
         """Load new weights: copied into the parameter buffer the engines (and the
