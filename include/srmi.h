@@ -472,6 +472,58 @@ int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* d
 int srmi_rmse_partial_masked(srmi_engine* e, const float* pred, const float* target, size_t n, float* loss4,
                              void* stream);
 
+/* ---- land in training (no reference counterpart: the reference drops every tile that
+ * touches land, and its losses know no mask) ------------------------------------ */
+/* srmi_tiles_nonfinite with a threshold, on the same floor grid (ncells = (H/ty) (W/tx)):
+ * nwet[c*ncells + t] (optional) = the finite pixels of tile t of channel c;
+ * bad[c*ncells + t] = 1 iff SOME channel of tile t has nwet < min_wet -- the same flag in
+ * every channel's row, so srmi_tiles_keep / srmi_tiles_gather_dev take it unchanged and
+ * the keep list stays channel-aligned.  Every flag and count is stored (no memset
+ * needed), no atomics.  With min_wet = ty * tx and channels that share a mask it equals
+ * srmi_tiles_nonfinite.  min_wet < 1: SRMI_ERR_ARG. */
+int srmi_tiles_dry(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
+                   void* stream);
+/* The flood fill of srmi_region_to_tiles_overlap_masked (the same device function: add
+ * order, fp32(1 / count), simultaneous passes), in place on tiles [nplanes][h][w]: every
+ * non-finite pixel of a plane is filled from the finite ones.  A plane without a
+ * non-finite pixel is not written; a plane without a finite pixel becomes 0.0f.  passes
+ * [nplanes] (optional) = the pass count, 0 for the former, -1 for the latter.  Any
+ * nplanes; h * w <= 25600 (the plane and its stamps in LDS), else SRMI_ERR_SHAPE.  The
+ * trip count is decided on the device: no host read, capturable. */
+int srmi_tiles_fill(float* tiles, long long nplanes, int h, int w, int* passes, void* stream);
+/* srmi_batch_prep_norm for tiles with land (non-finite = dry).  The statistics run over
+ * the wet pixels with the arithmetic of the masked cut: LNORM fp64 mean and 2-pass
+ * variance / nwet, x' = (float)(((double)x - mean) * (1 / std)), off_out = mean, div_out =
+ * std; LSCALE (min, max over the wet pixels) and AFFINE as srmi_batch_prep_norm, whose
+ * hr, lr, off_out and div_out they give bit for bit when no input is non-finite.  hr =
+ * the normalised, xy-flipped tile with the canonical NaN at the dry pixels; lr (optional)
+ * = srmi_downsample's arithmetic on that tile (an LR pixel is non-finite iff one of its
+ * 4 x 4 taps is dry) and then srmi_tiles_fill, a second launch; nwet [B][C] (optional) = the
+ * wet pixels.  A plane without a wet pixel: hr all NaN, lr all 0.0f, IEEE statistics.
+ * Errors as srmi_batch_prep_norm (every mode takes any B with B * C < 2^31 and needs
+ * 16-byte aligned raw and hr); (T / scale)^2 > 25600 with lr: SRMI_ERR_SHAPE. */
+int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
+                           const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
+                           int* nwet, void* stream);
+/* srmi_tile_loss_parts over the elements where pred and target are both finite: the same
+ * slices, reduction tree and parts[ntiles][16], plus cparts[ntiles][16] = the number of
+ * such elements per slice as floats (exact: a slice holds tile_elems / 16 elements).  On
+ * all-finite inputs parts is srmi_tile_loss_parts' bit for bit. */
+int srmi_tile_loss_parts_masked(const float* pred, const float* target, int ntiles, long long tile_elems, int kind,
+                                float eps, float* parts, float* cparts, void* stream);
+/* srmi_loss_from_parts with the count read from the device: loss4[1] = the sum of the
+ * ntiles x 16 cparts (fp64; whole numbers, exact).  kind -1: not finalised.  On
+ * all-finite inputs loss4 is srmi_loss_from_parts' with the host count, bit for bit; a
+ * count of 0 gives the IEEE result, as srmi_rmse_partial_masked. */
+int srmi_loss_from_parts_masked(const float* parts, const float* cparts, int ntiles, int kind, float* loss4,
+                                void* stream);
+/* The upstream gradient srmi_backward takes as dy, from a finalised loss4, +0.0f where
+ * pred or target is not finite.  RMSE: (p - t) * loss4[2] in fp32 -- exactly what the tail
+ * kernels form on the fly from sr / hr / loss4.  MEAN (Charbonnier): d / sqrt(d^2 + eps) *
+ * (float)(1 / loss4[1]), srmi_charbonnier_partial's dy. */
+int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int kind, float eps, const float* loss4,
+                        float* dy, void* stream);
+
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)
  * -> hr [B][C][T][T] = xyflip(lnorm(raw)) (norm 'lnorm' raw.py:169-181: per tile

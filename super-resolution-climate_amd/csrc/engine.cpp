@@ -1599,6 +1599,41 @@ int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* d
   return tiles_blend_masked_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, S_(stream));
 }
 
+int srmi_tiles_dry(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
+                   void* stream) {
+  return tiles_dry_launch(region, C, H, W, ty, tx, min_wet, bad, nwet, S_(stream));
+}
+
+int srmi_tiles_fill(float* tiles, long long nplanes, int h, int w, int* passes, void* stream) {
+  return tiles_fill_launch(tiles, nplanes, h, w, passes, S_(stream));
+}
+
+int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
+                           const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
+                           int* nwet, void* stream) {
+  return batch_prep_masked_launch(raw, B, C, T, flip_index, scale, mode, off, div, hr, lr, off_out, div_out, nwet,
+                                  S_(stream));
+}
+
+int srmi_tile_loss_parts_masked(const float* pred, const float* target, int ntiles, long long tile_elems, int kind,
+                                float eps, float* parts, float* cparts, void* stream) {
+  if (!pred || !target || !parts || !cparts || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN))
+    return SRMI_ERR_ARG;
+  return tile_loss_parts_masked_launch(pred, target, ntiles, tile_elems, kind, eps, parts, cparts, S_(stream));
+}
+
+int srmi_loss_from_parts_masked(const float* parts, const float* cparts, int ntiles, int kind, float* loss4,
+                                void* stream) {
+  if (!parts || !cparts || !loss4 || ntiles < 1 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
+  return loss_from_parts_masked_launch(parts, cparts, ntiles * kTileSub, kind, loss4, S_(stream));
+}
+
+int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int kind, float eps, const float* loss4,
+                        float* dy, void* stream) {
+  if (!pred || !target || !loss4 || !dy || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  return loss_dy_masked_launch(pred, target, n, kind, eps, loss4, dy, S_(stream));
+}
+
 int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {
   return tile_stats_launch(tiles, n, C, ty, tx, acc, first, S_(stream));
 }

@@ -1196,6 +1196,123 @@ int loss_from_parts_launch(const float* parts, int nparts, double count, int kin
   return 0;
 }
 
+// The three above for training on tiles with land (no reference counterpart: the
+// reference's losses know no mask).  tile_loss_parts_masked_kernel is
+// tile_loss_parts_kernel -- its slices, its reduction tree -- over the elements where y
+// and t are both finite, with their count beside it in cparts (an int per thread and
+// slice, stored as a float: exact, a slice holds tile_elems / 16 elements); an
+// all-finite pair gives tile_loss_parts_kernel's bits.
+__global__ void __launch_bounds__(256) tile_loss_parts_masked_kernel(const float* __restrict__ y,
+                                                                     const float* __restrict__ t,
+                                                                     long long tile_elems, int kind, float eps,
+                                                                     float* __restrict__ parts,
+                                                                     float* __restrict__ cparts) {
+  __shared__ float red[4];
+  __shared__ int redk[4];
+  const int sub = blockIdx.x, tile = blockIdx.y;
+  const long long per = (tile_elems + kTileSub - 1) / kTileSub;
+  const long long i0 = (long long)sub * per, i1 = min(tile_elems, i0 + per);
+  const size_t base = (size_t)tile * (size_t)tile_elems;
+  float s = 0.f;
+  int k = 0;
+  for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const float a = y[base + i], b = t[base + i];
+    if (isfinite(a) && isfinite(b)) {
+      const float d = a - b;
+      s += kind == LOSS_MEAN ? sqrtf(d * d + eps) : d * d;
+      ++k;
+    }
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = s;
+    redk[threadIdx.x >> 6] = k;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    parts[(size_t)tile * kTileSub + sub] = (red[0] + red[1]) + (red[2] + red[3]);
+    cparts[(size_t)tile * kTileSub + sub] = (float)((redk[0] + redk[1]) + (redk[2] + redk[3]));
+  }
+}
+
+int tile_loss_parts_masked_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind,
+                                  float eps, float* parts, float* cparts, hipStream_t st) {
+  if (ntiles < 1 || tile_elems < 1) return SRMI_ERR_SHAPE;
+  hipLaunchKernelGGL(tile_loss_parts_masked_kernel, dim3(kTileSub, ntiles), dim3(256), 0, st, y, t, tile_elems, kind,
+                     eps, parts, cparts);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// loss_from_parts_kernel with the count read from the device: the sum of cparts, by the
+// same tree in fp64 (whole numbers: exact in any order).  Count 0: the IEEE result.
+__global__ void __launch_bounds__(256) loss_from_parts_masked_kernel(const float* __restrict__ parts,
+                                                                     const float* __restrict__ cparts, int nparts,
+                                                                     int kind, float* loss) {
+  __shared__ double red[2][256];
+  const int tid = threadIdx.x;
+  const int per = (nparts + 255) / 256, i0 = tid * per, i1 = min(nparts, i0 + per);
+  double a = 0.0, c = 0.0;
+  for (int i = i0; i < i1; ++i) {
+    a += parts[i];
+    c += cparts[i];
+  }
+  red[0][tid] = a;
+  red[1][tid] = c;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      red[0][tid] += red[0][tid + o];
+      red[1][tid] += red[1][tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    loss[0] = (float)red[0][0];
+    loss[1] = (float)red[1][0];
+    if (kind >= 0) loss_finalize_one(loss, kind);
+  }
+}
+
+int loss_from_parts_masked_launch(const float* parts, const float* cparts, int nparts, int kind, float* loss,
+                                  hipStream_t st) {
+  if (nparts < 1) return SRMI_ERR_ARG;
+  hipLaunchKernelGGL(loss_from_parts_masked_kernel, dim3(1), dim3(256), 0, st, parts, cparts, nparts, kind, loss);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// The upstream gradient of the masked loss from a finalised loss4, 0.0f where y or t is
+// not finite.  RMSE: (y - t) * loss[2], the fp32 expression tail_dgrad_kernel and
+// tail_wgrad_lds_kernel form on the fly.  MEAN: charb_partial_kernel's d / r * inv_count
+// with inv_count = (float)(1.0 / count) formed from loss[1] as its launcher forms it.
+__global__ void __launch_bounds__(256) loss_dy_masked_kernel(const float* __restrict__ y, const float* __restrict__ t,
+                                                             size_t n, int kind, float eps,
+                                                             const float* __restrict__ loss, float* __restrict__ dy) {
+  const float sc = kind == LOSS_MEAN ? (float)(1.0 / (double)loss[1]) : loss[2];
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float a = y[i], b = t[i];
+    float g = 0.f;
+    if (isfinite(a) && isfinite(b)) {
+      const float d = a - b;
+      g = kind == LOSS_MEAN ? d / sqrtf(d * d + eps) * sc : d * sc;
+    }
+    dy[i] = g;
+  }
+}
+
+int loss_dy_masked_launch(const float* y, const float* t, size_t n, int kind, float eps, const float* loss, float* dy,
+                          hipStream_t st) {
+  if (n < 1) return SRMI_ERR_SHAPE;
+  const size_t nblk = (n + 255) / 256;
+  hipLaunchKernelGGL(loss_dy_masked_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, y, t, n,
+                     kind, eps, loss, dy);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
 int batch_loss_means_launch(const float* sums, int ntiles, long long tile_elems, int bs, int kind, float* out,
                             hipStream_t st) {
   if (ntiles < 1 || tile_elems < 1 || bs < 1 || (ntiles + bs - 1) / bs > 1024) return SRMI_ERR_SHAPE;

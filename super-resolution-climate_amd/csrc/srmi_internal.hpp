@@ -215,6 +215,14 @@ int tile_loss_parts_launch(const float* y, const float* t, int ntiles, long long
 int loss_from_parts_launch(const float* parts, int nparts, double count, int kind, float* loss, hipStream_t st);
 int charb_partial_launch(const float* y, const float* t, size_t n, float eps, double count, float* dy,
                          float* partial, int nblk, hipStream_t st);
+// the same over the elements where y and t are both finite (training on tiles with land):
+// the count rides in cparts and is summed on the device; dy from the finalised loss
+int tile_loss_parts_masked_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind,
+                                  float eps, float* parts, float* cparts, hipStream_t st);
+int loss_from_parts_masked_launch(const float* parts, const float* cparts, int nparts, int kind, float* loss,
+                                  hipStream_t st);
+int loss_dy_masked_launch(const float* y, const float* t, size_t n, int kind, float eps, const float* loss, float* dy,
+                          hipStream_t st);
 
 // channel attention
 // residual stream: fp32 h_in / h_out, or (bf16 engine) as a bf16 hi + lo pair: lo_out
@@ -300,6 +308,13 @@ int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int
 int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
                               int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
                               hipStream_t st);
+// land in training: the keep flags with a threshold, the fill in place, the masked prep
+int tiles_dry_launch(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
+                     hipStream_t st);
+int tiles_fill_launch(float* tiles, long long nplanes, int h, int w, int* passes, hipStream_t st);
+int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                             const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                             int* nwet, hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

@@ -999,6 +999,7 @@ constexpr int kLandMaxPix = 25600;  // 6 bytes a pixel in 150 KiB of LDS (160 x 
 constexpr unsigned short kLandDry = 0xffffu;
 __constant__ float kLandRecip[8] = {1.f, 1.f / 2.f, 1.f / 3.f, 1.f / 4.f, 1.f / 5.f, 1.f / 6.f, 1.f / 7.f, 1.f / 8.f};
 
+static_assert(kPrepThreads == kLandThreads, "block_sum_i32 also serves the kPrepThreads kernels");
 __device__ __forceinline__ int block_sum_i32(int v, int* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -1009,6 +1010,50 @@ __device__ __forceinline__ int block_sum_i32(int v, int* red) {
   for (int i = 0; i < kLandThreads / 64; ++i) s += red[i];
   __syncthreads();
   return s;
+}
+
+// The flood fill described above, on a ty x tx plane in LDS (val, and stamp: 0 = wet,
+// kLandDry = not filled yet), by the kLandThreads threads of a workgroup; a thread owns
+// the pixels tid, tid + kLandThreads, ...  The caller has a barrier between its last
+// store to the plane and this call; the stores of the last pass are ordered by the
+// barrier that ends it.  Needs a wet pixel.  Returns the number of passes that filled
+// something (1 for a plane without a dry pixel: the one pass that finds nothing to do).
+// Shared by the masked cut and srmi_tiles_fill, so the two fill bit for bit alike.
+__device__ __forceinline__ int land_fill(float* val, unsigned short* stamp, int ty, int tx) {
+  const int n = ty * tx, tid = threadIdx.x;
+  const int jmax = max(ty, tx);
+  int j = 1;
+  for (; j < jmax; ++j) {
+    int left = 0;
+    for (int i = tid; i < n; i += kLandThreads) {
+      if (stamp[i] != kLandDry) continue;
+      const int y = i / tx, x = i - y * tx;
+      float acc = 0.f;
+      int cnt = 0;
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+          if (dy == 0 && dx == 0) continue;
+          const int yy = y + dy, xx = x + dx;
+          if (yy < 0 || yy >= ty || xx < 0 || xx >= tx) continue;
+          const int q = yy * tx + xx;
+          if ((int)stamp[q] < j) {
+            acc += val[q];
+            ++cnt;
+          }
+        }
+      }
+      if (cnt) {
+        val[i] = acc * kLandRecip[cnt - 1];
+        stamp[i] = (unsigned short)j;
+      } else {
+        left = 1;
+      }
+    }
+    if (__syncthreads_count(left) == 0) break;
+  }
+  return j;
 }
 
 template <int kMode, bool kVec>
@@ -1117,37 +1162,7 @@ __global__ void __launch_bounds__(kLandThreads) region_to_tiles_masked_kernel(
     if (stamp[i] == 0) val[i] = (float)(((double)val[i] - o) * inv);
   __syncthreads();
   // 5. flood fill; not bad => nwet >= min_wet >= 1, so it ends within max(ty, tx) - 1 passes
-  const int jmax = max(ty, tx);
-  for (int j = 1; j < jmax; ++j) {
-    int left = 0;
-    for (int i = tid; i < n; i += kLandThreads) {
-      if (stamp[i] != kLandDry) continue;
-      const int y = i / tx, x = i - y * tx;
-      float acc = 0.f;
-      int cnt = 0;
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy) {
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-          if (dy == 0 && dx == 0) continue;
-          const int yy = y + dy, xx = x + dx;
-          if (yy < 0 || yy >= ty || xx < 0 || xx >= tx) continue;
-          const int q = yy * tx + xx;
-          if ((int)stamp[q] < j) {
-            acc += val[q];
-            ++cnt;
-          }
-        }
-      }
-      if (cnt) {
-        val[i] = acc * kLandRecip[cnt - 1];
-        stamp[i] = (unsigned short)j;
-      } else {
-        left = 1;
-      }
-    }
-    if (__syncthreads_count(left) == 0) break;
-  }
+  land_fill(val, stamp, ty, tx);
   // 6. the tile, once
   if (kVec) {
     float4* d4 = reinterpret_cast<float4*>(dst);
@@ -1189,6 +1204,219 @@ int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int
   }
 #undef SRMI_R2T_MASKED
   SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------- land in training batches
+// No reference counterpart (the reference never trains on a tile with land).
+//
+// tiles_fill: the fill above, in place on [nplanes][h][w] planes that already are what
+// the forward takes (the LR batch of a train step).  One workgroup per plane, planes
+// blockIdx.x, + gridDim.x, ... (any number of them, as the resampling kernels); the plane
+// and its stamps in LDS as in the cut.  A plane without a non-finite pixel is not
+// written at all, one without a finite pixel becomes 0.0f (what the cut gives a bad
+// tile); of the others only the filled pixels are stored.  passes (optional): the pass
+// count, 0 and -1 for those two.  The trip count stays on the device.
+__global__ void __launch_bounds__(kLandThreads) tiles_fill_kernel(float* __restrict__ tiles, long long nplanes, int h,
+                                                                  int w, int* __restrict__ passes) {
+  extern __shared__ float tile[];  // val[h * w], then the stamps
+  __shared__ int redi[kLandThreads / 64];
+  const int tid = threadIdx.x, n = h * w;
+  float* val = tile;
+  unsigned short* stamp = reinterpret_cast<unsigned short*>(tile + n);
+  for (long long p = blockIdx.x; p < nplanes; p += gridDim.x) {
+    float* pl = tiles + (size_t)p * n;
+    int k = 0;
+    for (int i = tid; i < n; i += kLandThreads) {
+      const float a = pl[i];
+      const bool wet = isfinite(a);
+      val[i] = a;
+      stamp[i] = wet ? 0 : kLandDry;
+      k += !wet;
+    }
+    const int ndry = block_sum_i32(k, redi);  // (also orders the LDS stores)
+    int np = 0;
+    if (ndry == n) {
+      for (int i = tid; i < n; i += kLandThreads) pl[i] = 0.f;
+      np = -1;
+    } else if (ndry) {  // (uniform over the block)
+      np = land_fill(val, stamp, h, w);
+      for (int i = tid; i < n; i += kLandThreads)
+        if (stamp[i] != 0) pl[i] = val[i];
+    }
+    if (passes && tid == 0) passes[p] = np;
+    __syncthreads();  // the next plane overwrites the LDS
+  }
+}
+
+int tiles_fill_launch(float* tiles, long long nplanes, int h, int w, int* passes, hipStream_t st) {
+  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
+  if ((long long)h * w > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
+  if (!tiles) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)h * w * (sizeof(float) + sizeof(unsigned short));
+  const unsigned grid = (unsigned)(nplanes < 65535 ? nplanes : 65535);
+  hipLaunchKernelGGL(tiles_fill_kernel, dim3(grid), dim3(kLandThreads), lds, st, tiles, nplanes, h, w, passes);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// batch_prep_norm_kernel for tiles with land: the statistics over the wet (finite)
+// pixels with the arithmetic of the masked cut (LNORM: fp64 mean and 2-pass variance over
+// nwet; LSCALE / AFFINE: batch_prep_norm_kernel's, so tiles without a non-finite value
+// give its bits), the flipped HR tile with the canonical NaN at the dry pixels, and the
+// LR tile by downsample_kernel's arithmetic on it -- an LR pixel is NaN iff one of its
+// taps is dry.  The LR planes are then filled by tiles_fill_kernel, a second launch: the
+// 192^2 HR plane takes 145 of the 150 KiB of LDS this kernel may use, and the LR plane
+// with its stamps does not fit beside it.
+template <bool kLds, int kMode>
+__global__ void __launch_bounds__(kPrepThreads) batch_prep_masked_kernel(
+    const float* __restrict__ raw, int T, int flip, int scale, const float* __restrict__ off,
+    const float* __restrict__ dv, float* __restrict__ hr, float* __restrict__ lr, float* __restrict__ off_out,
+    float* __restrict__ div_out, int* __restrict__ nwet) {
+  extern __shared__ float tile[];  // [T][T + 1] when kLds
+  __shared__ double red[kPrepThreads / 64];
+  __shared__ float redf[2 * kPrepThreads / 64];
+  __shared__ int redi[kPrepThreads / 64];
+  const size_t p = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int n = T * T, P = kLds ? T + 1 : T;
+  const float* src = raw + p * n;
+  const float* buf = kLds ? tile : src;
+  float mn = INFINITY, mx = -INFINITY;
+  double s = 0.0;
+  int k = 0;
+  auto take = [&](float a) __attribute__((always_inline)) {
+    if (isfinite(a)) {
+      ++k;
+      if (kMode == SRMI_NORM_LNORM) s += (double)a;
+      if (kMode == SRMI_NORM_LSCALE) {
+        mn = fminf(mn, a);
+        mx = fmaxf(mx, a);
+      }
+    }
+  };
+  for (int i = 4 * tid; i < n; i += 4 * kPrepThreads) {  // T even -> n % 4 == 0
+    const float4 v = *reinterpret_cast<const float4*>(src + i);
+    take(v.x);
+    take(v.y);
+    take(v.z);
+    take(v.w);
+    if (kLds) {
+      const int y = i / T, x = i - y * T;
+      if (x + 3 < T) {
+        float* d = tile + y * P + x;
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+      } else {  // T % 4 == 2: the float4 straddles two rows
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+        for (int e = 0; e < 4; ++e) {
+          const int ye = (i + e) / T, xe = (i + e) - ye * T;
+          tile[ye * P + xe] = vv[e];
+        }
+      }
+    }
+  }
+  const int nw = block_sum_i32(k, redi);  // (also orders the LDS stores)
+  double o, inv, sd = 0.0;
+  if (kMode == SRMI_NORM_LNORM) {
+    o = block_sum_f64<kPrepThreads>(s, red) / (double)nw;
+    double q = 0.0;
+    for (int i = tid; i < n; i += kPrepThreads) {
+      const int y = i / T, x = i - y * T;
+      const float a = buf[y * P + x];
+      if (isfinite(a)) {
+        const double d = (double)a - o;
+        q += d * d;
+      }
+    }
+    sd = sqrt(block_sum_f64<kPrepThreads>(q, red) / (double)nw);
+    inv = 1.0 / sd;
+  } else if (kMode == SRMI_NORM_LSCALE) {
+    block_minmax<kPrepThreads>(mn, mx, redf);
+    o = (double)mn;
+    inv = 1.0 / ((double)mx - (double)mn);
+  } else {
+    o = (double)off[p];
+    inv = 1.0 / (double)dv[p];
+  }
+  // batch_prep_norm_kernel's expression, as it stands there: a NaN stays a NaN through it
+  // and an infinity stays non-finite, so the HR tile needs a select and the LR taps none
+  auto norm = [&](int y, int x) __attribute__((always_inline)) {
+    int sy, sx;
+    flip_src(flip, T, y, x, sy, sx);
+    return (float)(((double)buf[sy * P + sx] - o) * inv);
+  };
+  float* dst = hr + p * n;
+  for (int i = 4 * tid; i < n; i += 4 * kPrepThreads) {
+    float q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int y = (i + e) / T, x = (i + e) - y * T;
+      int sy, sx;
+      flip_src(flip, T, y, x, sy, sx);
+      q[e] = isfinite(buf[sy * P + sx]) ? norm(y, x) : __int_as_float(0x7fc00000);
+    }
+    *reinterpret_cast<float4*>(dst + i) = make_float4(q[0], q[1], q[2], q[3]);
+  }
+  if (lr) {
+    // downsample_kernel's arithmetic (small.hip), tap order as in batch_prep_kernel; a dry
+    // tap makes the pixel non-finite (NaN, or an infinity's), which is all the fill asks
+    const int t = T / scale;
+    const float kk[4] = {-3.f / 32.f, 19.f / 32.f, 19.f / 32.f, -3.f / 32.f};
+    float* ldst = lr + p * t * t;
+    for (int i = tid; i < t * t; i += kPrepThreads) {
+      const int y = i / t, x = i - y * t;
+      const int y0 = y * scale + scale / 2 - 2, x0 = x * scale + scale / 2 - 2;
+      float acc = 0.f;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int yy = min(max(y0 + a, 0), T - 1);
+        float rsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rsum += kk[j] * norm(yy, min(max(x0 + j, 0), T - 1));
+        acc += kk[a] * rsum;
+      }
+      ldst[i] = acc;
+    }
+  }
+  if (tid == 0) {
+    if (nwet) nwet[p] = nw;
+    if (kMode == SRMI_NORM_LNORM) {
+      if (off_out) off_out[p] = (float)o;
+      if (div_out) div_out[p] = (float)sd;
+    } else if (kMode == SRMI_NORM_LSCALE) {
+      if (off_out) off_out[p] = mn;
+      if (div_out) div_out[p] = mx - mn;
+    }
+  }
+}
+
+int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                             const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                             int* nwet, hipStream_t st) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
+  if (lr && (long long)(T / scale) * (T / scale) > kLandMaxPix) return SRMI_ERR_SHAPE;  // tiles_fill's plane
+  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
+  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
+  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
+#define SRMI_PREP_MASKED(LDS, MODE, BYTES)                                                                          \
+  hipLaunchKernelGGL((batch_prep_masked_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
+                     lr, off_out, div_out, nwet)
+  if (lds <= 150 * 1024) {
+    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(true, SRMI_NORM_LNORM, lds);
+    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(true, SRMI_NORM_LSCALE, lds);
+    else SRMI_PREP_MASKED(true, SRMI_NORM_AFFINE, lds);
+  } else {
+    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(false, SRMI_NORM_LNORM, 0);
+    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(false, SRMI_NORM_LSCALE, 0);
+    else SRMI_PREP_MASKED(false, SRMI_NORM_AFFINE, 0);
+  }
+#undef SRMI_PREP_MASKED
+  SRMI_CHECK_LAUNCH();
+  if (lr) return tiles_fill_launch(lr, B * C, T / scale, T / scale, nullptr, st);
   return 0;
 }
 
@@ -1369,6 +1597,46 @@ int tiles_nonfinite_launch(const float* region, int C, int H, int W, int ty, int
   if (!region || !bad) return SRMI_ERR_ARG;
   hipLaunchKernelGGL(tiles_nonfinite_kernel, dim3((H / ty) * (W / tx), C), dim3(256), 0, st, region, H, W, ty, tx,
                      W / tx, bad);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// tiles_nonfinite_kernel with a threshold, for training on coastal tiles (no reference
+// counterpart: get_tiles drops a tile for one NaN).  nwet[c * ncells + t] = the finite
+// pixels of plane (c, t); a tile is bad when SOME channel has fewer than min_wet, and
+// that one flag goes into every channel's row, so the keep list that tiles_keep_kernel
+// makes of it stays channel-aligned.  One workgroup counts all the channels of a tile
+// and stores with plain stores -- for the masked cut's reason, neither a memset nor an
+// atomic.  grid (ncells)
+__global__ void __launch_bounds__(256) tiles_dry_kernel(const float* __restrict__ region, int C, int H, int W, int ty,
+                                                        int tx, int gx, int min_wet, int* __restrict__ bad,
+                                                        int* __restrict__ nwet) {
+  __shared__ int red[4];
+  const int t = blockIdx.x, ncells = gridDim.x;
+  const int y0 = (t / gx) * ty, x0 = (t % gx) * tx;
+  int isbad = 0;
+  for (int c = 0; c < C; ++c) {
+    const float* src = region + (size_t)c * H * W + (size_t)y0 * W + x0;
+    int k = 0;
+    for (int i = threadIdx.x; i < ty * tx; i += 256) k += isfinite(src[(size_t)(i / tx) * W + (i % tx)]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = k;
+    __syncthreads();
+    const int nw = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    if (nwet && threadIdx.x == 0) nwet[(size_t)c * ncells + t] = nw;
+    isbad |= nw < min_wet;
+  }
+  for (int c = threadIdx.x; c < C; c += 256) bad[(size_t)c * ncells + t] = isbad;
+}
+
+int tiles_dry_launch(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
+                     hipStream_t st) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  if (!region || !bad || min_wet < 1) return SRMI_ERR_ARG;
+  hipLaunchKernelGGL(tiles_dry_kernel, dim3((H / ty) * (W / tx)), dim3(256), 0, st, region, C, H, W, ty, tx, W / tx,
+                     min_wet, bad, nwet);
   SRMI_CHECK_LAUNCH();
   return 0;
 }

@@ -125,6 +125,13 @@ _SIGS = {
     "srmi_tiles_blend_masked": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int,
                                  P, P], C.c_int),
     "srmi_rmse_partial_masked": ([P, P, P, C.c_size_t, P, P], C.c_int),
+    "srmi_tiles_dry": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P], C.c_int),
+    "srmi_tiles_fill": ([P, C.c_longlong, C.c_int, C.c_int, P, P], C.c_int),
+    "srmi_batch_prep_masked": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P],
+                               C.c_int),
+    "srmi_tile_loss_parts_masked": ([P, P, C.c_int, C.c_longlong, C.c_int, C.c_float, P, P, P], C.c_int),
+    "srmi_loss_from_parts_masked": ([P, P, C.c_int, C.c_int, P, P], C.c_int),
+    "srmi_loss_dy_masked": ([P, P, C.c_size_t, C.c_int, C.c_float, P, P, P], C.c_int),
     "srmi_tile_stats": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, P, C.c_int, P], C.c_int),
     "srmi_tile_stats_finalize": ([P, C.c_longlong, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_llc_index_map_workspace": ([C.c_longlong, C.POINTER(C.c_size_t)], C.c_int),

@@ -50,7 +50,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr
-from .llc import LLCSource
+from .llc import LLCSource, min_wet_pixels
 
 MAX_READERS = 4
 _IDLE, _READING, _LOADED, _ENQUEUED = range(4)
@@ -83,13 +83,20 @@ class TimesliceFeed:
     """source: an LLCSource; paths[i]: the per-variable files of time slice i; tile:
     the (square) tile size.  depth slots, readers threads (at most MAX_READERS; never
     sized from the machine's CPU count), block_words / max_gap_blocks: the read plan
-    (LLCSource.read_plan).  Use as a context manager, or close()."""
+    (LLCSource.read_plan).  land / min_wet (a fraction of the tile plane): keep the
+    coastal tiles, as srmi.llc.get_tiles(min_wet=); land=False is the reference's rule.
+    Use as a context manager, or close()."""
 
     def __init__(self, source: LLCSource, paths: Sequence[Sequence[str]], tile: int, depth: int = 2,
                  readers: int = 2, block_words: int = 1024, max_gap_blocks: int = 0,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25):
         if depth < 1 or readers < 1:
             raise ValueError("TimesliceFeed: depth and readers must be at least 1")
+        # land: coastal tiles are kept (srmi_tiles_dry in place of srmi_tiles_nonfinite) when
+        # every channel has min_wet of the tile plane wet, and prepare() normalises them over
+        # their wet pixels (prep_batch(land=True)); train them with FusedTrainer(land=True)
+        self.land = bool(land)
+        self.min_wet = min_wet_pixels(min_wet, int(tile), int(tile)) if self.land else None
         if not paths or any(len(p) != len(paths[0]) or not len(p) for p in paths):
             raise ValueError("TimesliceFeed: every time slice needs the same, non-empty list of variable files")
         self.source = source
@@ -168,7 +175,11 @@ class TimesliceFeed:
             slot.h2d.record(st)
             for v in range(C):
                 call("srmi_llc_gather", ptr(slot.words[v]), plan.n_words, ptr(plan.idx), npix, ptr(slot.region[v]), h)
-            call("srmi_tiles_nonfinite", ptr(slot.region), C, self.ys, self.xs, self.ty, self.tx, ptr(slot.bad), h)
+            if self.land:
+                call("srmi_tiles_dry", ptr(slot.region), C, self.ys, self.xs, self.ty, self.tx, self.min_wet,
+                     ptr(slot.bad), None, h)
+            else:
+                call("srmi_tiles_nonfinite", ptr(slot.region), C, self.ys, self.xs, self.ty, self.tx, ptr(slot.bad), h)
             call("srmi_tiles_keep", ptr(slot.bad), C, self.ncells, ptr(slot.src), ptr(slot.count), h)
             call("srmi_tiles_gather_dev", ptr(slot.region), C, self.ys, self.xs, self.ty, self.tx, ptr(slot.src),
                  ptr(slot.count), C * self.ncells, ptr(slot.tiles), h)
@@ -259,8 +270,13 @@ class TimesliceFeed:
 
     def norm_stats(self):
         """One pass over the slices -> the finalised srmi.norm.NormStats the dataset
-        norm modes (gnorm, gscale, tnorm, tscale) need."""
+        norm modes (gnorm, gscale, tnorm, tscale) need.  A land feed raises: its tiles
+        hold NaN, and srmi_tile_stats over them is NaN."""
         from .norm import NormStats
+        if self.land:
+            raise ValueError("norm_stats: the tiles of a land=True feed hold NaN; compute the statistics with a "
+                             "land=False TimesliceFeed over the same files and pass them as stats= (the gnorm / "
+                             "gscale constants do not depend on the tile)")
         return NormStats.compute(self.timeslices())
 
     def prepare(self, norm: str = "lnorm", stats=None, scale: Optional[int] = None
@@ -281,7 +297,7 @@ class TimesliceFeed:
             hr = self._hr[:b]
             if b:
                 prep_batch(raw, flip_index, 4 if scale is None else int(scale), with_lr=False, hr=hr, norm=norm,
-                           stats=stats, tile_range=(start, start + b))
+                           stats=stats, tile_range=(start, start + b), land=self.land)
             self.poll()
             return hr
         return prep

@@ -222,7 +222,11 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
     TimesliceFeed.prepare makes one).  Rank 0 draws the time slice's flips with
     xyflip_index(xyflip, rng) right after the shuffle, one per batch in batch order
     -- the order one reference process consumes `random` -- and they are broadcast
-    with the starts, so every rank prepares the same flip."""
+    with the starts, so every rank prepares the same flip.
+
+    Tiles with land need nothing here: a TimesliceFeed(land=True) returns raw tiles
+    whose NaN are the mask, its prepare() normalises them over their wet pixels, and a
+    FusedTrainer(land=True) steps them; this loop only slices and passes them on."""
     from .batch import xyflip_index
     from .dist import DistInfo, barrier, broadcast_ints, shard_capacity, shard_range
     info = getattr(trainer, "info", None) or DistInfo()

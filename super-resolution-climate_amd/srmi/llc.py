@@ -26,6 +26,7 @@ reads whole files.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -190,17 +191,35 @@ class LLCReadPlan:
             os.close(fd)
 
 
-def get_tiles(region: torch.Tensor, ty: int, tx: int) -> Tuple[torch.Tensor, np.ndarray, Tuple[int, int]]:
+def min_wet_pixels(min_wet: float, ty: int, tx: int) -> int:
+    """A min_wet fraction of the ty x tx tile plane as the pixel count the C ABI takes:
+    max(1, ceil(min_wet * ty * tx)), as srmi.superres."""
+    if not 0.0 < float(min_wet) <= 1.0:
+        raise ValueError(f"min_wet {min_wet!r} outside (0, 1]")
+    return max(1, int(math.ceil(float(min_wet) * ty * tx)))
+
+
+def get_tiles(region: torch.Tensor, ty: int, tx: int,
+              min_wet: Optional[float] = None) -> Tuple[torch.Tensor, np.ndarray, Tuple[int, int]]:
     """get_tiles (raw.py:216-233) on a device region [C, H, W] -> (tiles [n//C, C,
     ty, tx], tile ids (the first n//C kept ids of the channel-major flattening, as
     the reference's coords), (gy, gx)).  One host sync for the keep mask (the
-    reference does this once per time slice)."""
+    reference does this once per time slice).
+
+    min_wet (no reference counterpart; None: the reference's rule, one non-finite value
+    drops the tile): a fraction of the tile plane.  A tile is kept when every channel has
+    at least max(1, ceil(min_wet * ty * tx)) finite pixels (srmi_tiles_dry); the kept
+    tiles hold their NaN, for prep_batch(land=True) and FusedTrainer(land=True)."""
     if region.dtype != torch.float32 or region.dim() != 3 or not region.is_contiguous():
         raise ValueError("get_tiles: region must be a contiguous fp32 [C, H, W] device tensor")
     Cn, H, W = region.shape
     gy, gx = H // ty, W // tx
     bad = torch.empty(Cn * gy * gx, dtype=torch.int32, device=region.device)
-    call("srmi_tiles_nonfinite", ptr(region), Cn, H, W, ty, tx, ptr(bad), stream_handle())
+    if min_wet is not None:
+        call("srmi_tiles_dry", ptr(region), Cn, H, W, ty, tx, min_wet_pixels(min_wet, ty, tx), ptr(bad), None,
+             stream_handle())
+    else:
+        call("srmi_tiles_nonfinite", ptr(region), Cn, H, W, ty, tx, ptr(bad), stream_handle())
     keep = np.flatnonzero(bad.cpu().numpy() == 0)
     n = keep.size // Cn
     src = torch.from_numpy(keep[:n * Cn].astype(np.int32)).to(region.device)

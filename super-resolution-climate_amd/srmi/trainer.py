@@ -70,7 +70,8 @@ class FusedTrainer:
                  eps: float = 1e-8, weight_decay: float = 0.0, interp_loss: bool = True,
                  info: Optional[DistInfo] = None, device: Optional[torch.device] = None, seed: int = 0,
                  params: Optional[torch.Tensor] = None, micro: Optional[int] = None, loss_fn: str = "l2",
-                 cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False):
+                 cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
+                 land: bool = False):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -84,7 +85,14 @@ class FusedTrainer:
         with each bucket's all-reduce behind its stage on an engine stream.
         task.downsample_mode / upsample_mode select the resampling of the model input
         and of the interp baseline ('cubic' -> bicubic, 'linear' -> bilinear,
-        array.py:37-41; others raise)."""
+        array.py:37-41; others raise).
+        land (no reference counterpart; DESIGN.md §1 "Land in training"): step() takes HR
+        tiles whose NaN are the land mask.  The LR input is formed as always and then
+        flood-filled in place (srmi_tiles_fill), the loss and the interp metric are taken
+        over the elements where prediction and target are both finite
+        (srmi_tile_loss_parts_masked, the count summed on the device), and the backward
+        runs from an upstream gradient that is zero on land (srmi_loss_dy_masked) for
+        both loss functions.  Refused with task.data_downsample > 1."""
         if loss_fn not in LOSS_KINDS:  # single_product_loss, dual_trainer.py:210-211
             raise ValueError(f"Unknown single-product loss function {loss_fn}")
         if task is None:
@@ -92,6 +100,10 @@ class FusedTrainer:
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
         tindx = check_fused_task(task, spec.nchannels_in, spec.nchannels_out)
         self.ds = data_downsample_factor(task)
+        self.land = bool(land)
+        if self.land and self.ds > 1:
+            raise ValueError(f"land=True with task.data_downsample={self.ds}: the land mask of a pre-downsampled "
+                             "HR batch is not defined (train on tiles of the model's own HR size)")
         self.dmode, self.umode = interp_mode(task, True), interp_mode(task, False)
         if tindx is not None and interp_loss and spec.nchannels_out != 1:
             # loss(btarget, upsample(binput)) (:315-317) needs equal or broadcastable channels
@@ -137,7 +149,8 @@ class FusedTrainer:
         self.up = (torch.empty((batch, C, h * s, w * s), dtype=torch.float32, device=self.device)
                    if interp_loss else None)
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
-        self.dy = torch.empty_like(self.sr) if self.loss_kind == SRMI_LOSS_MEAN else None
+        # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
+        self.dy = torch.empty_like(self.sr) if self.loss_kind == SRMI_LOSS_MEAN or self.land else None
         # the selected target channels (index_select) and, for the interp metric, that
         # target broadcast over the input's channels (1-channel target, :316-317)
         self.tgt = torch.empty_like(self.sr) if self.tindx is not None else None
@@ -156,7 +169,10 @@ class FusedTrainer:
         # (x + 0 is exact) hands every rank all of them, and every rank sums them in the
         # order one process would.
         self.gcap = batch * self.info.world
-        self.gparts = torch.zeros(2 * self.gcap * TILE_LOSS_SUB, dtype=torch.float32, device=self.device)
+        # land: the counts of the finite elements ride behind them, [loss | interp] again,
+        # through the same single all-reduce (whole numbers: x + 0 and their sums are exact)
+        self.gparts = torch.zeros((4 if self.land else 2) * self.gcap * TILE_LOSS_SUB, dtype=torch.float32,
+                                  device=self.device)
         self.streams = [None] + [engine_stream(self.device) for _ in range(micro - 1)]
         self.dp_staged = not dp_reducer_stream
         self.reducer = GradReducer(self.eng.table, spec.arch, spec.nlayers, self.info, self.device,
@@ -176,10 +192,16 @@ class FusedTrainer:
         st = self.streams[k]
         return torch.cuda.stream(st) if st is not None else _Null()
 
-    def _loss_parts(self, pred, target, parts, t0):
-        """This micro-batch's tiles' loss parts (rows t0.. of the batch-wide parts array)."""
+    def _loss_parts(self, pred, target, parts, t0, cparts=None):
+        """This micro-batch's tiles' loss parts (rows t0.. of the batch-wide parts array);
+        land: over the finite elements, their counts into the same rows of cparts."""
         nt = pred.shape[0]
         te = pred[0].numel()
+        if cparts is not None:
+            call("srmi_tile_loss_parts_masked", ptr(pred), ptr(target), nt, te, self.loss_kind, CHARBONNIER_EPS,
+                 ptr(parts[t0 * TILE_LOSS_SUB:]), ptr(cparts[t0 * TILE_LOSS_SUB:]),
+                 torch.cuda.current_stream(self.device).cuda_stream)
+            return
         call("srmi_tile_loss_parts", ptr(pred), ptr(target), nt, te, self.loss_kind, CHARBONNIER_EPS,
              ptr(parts[t0 * TILE_LOSS_SUB:]), torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -188,6 +210,16 @@ class FusedTrainer:
         order, finalised (data parallel: after the all-reduce of the parts)."""
         st = torch.cuda.current_stream(self.device).cuda_stream
         n = gb * TILE_LOSS_SUB
+        if self.land:  # [loss | interp] parts, then [loss | interp] counts; the count is the device's
+            m = 2 if self.interp_loss else 1
+            if self.info.enabled:
+                allreduce_sum_(self.gparts[:2 * m * n], self.info)
+            call("srmi_loss_from_parts_masked", ptr(self.gparts), ptr(self.gparts[m * n:]), gb, self.loss_kind,
+                 ptr(self.loss4), st)
+            if self.interp_loss:
+                call("srmi_loss_from_parts_masked", ptr(self.gparts[n:]), ptr(self.gparts[m * n + n:]), gb,
+                     self.loss_kind, ptr(self.iloss4), st)
+            return
         if self.info.enabled:
             allreduce_sum_(self.gparts[:2 * n if self.interp_loss else n], self.info)
         call("srmi_loss_from_parts", ptr(self.gparts), gb, float(count), self.loss_kind, ptr(self.loss4), st)
@@ -209,7 +241,8 @@ class FusedTrainer:
         return t0, gb
 
     def step(self, hr: torch.Tensor, shard: Optional[Tuple[int, int]] = None) -> Dict[str, torch.Tensor]:
-        """hr: this rank's HR tiles [b, C, H, W] fp32 on the device (already normalised),
+        """hr: this rank's HR tiles [b, C, H, W] fp32 on the device (already normalised;
+        land=True: NaN on land),
         b <= the trainer's batch (a short last batch of a time slice, as the
         reference's TileBatchIterator yields, sres/data/tiles.py:55-72).
 
@@ -242,8 +275,14 @@ class FusedTrainer:
         icount = float(gb) * self.lrbuf[0].numel() * s * s
         n = gb * TILE_LOSS_SUB
         lparts, iparts = self.gparts[:n], self.gparts[n:2 * n]
+        lcparts = icparts = None
+        if self.land:
+            # [loss | interp | loss counts | interp counts] of n each; without the interp
+            # metric [loss | loss counts]: iparts above then overlaps lcparts and is not used
+            m = 2 if self.interp_loss else 1
+            lcparts, icparts = self.gparts[m * n:m * n + n], self.gparts[m * n + n:m * n + 2 * n]
         if self.info.enabled:  # the other ranks' tiles' parts stay 0 here
-            self.gparts[:2 * n].zero_()
+            self.gparts[:(4 if self.land else 2) * n].zero_()
         for st in self.streams[1:]:
             st.wait_stream(main)
         # forward + loss partials per micro-batch (an empty micro-batch adds nothing)
@@ -253,19 +292,31 @@ class FusedTrainer:
                 continue
             with self._ctx(k):
                 downsample(hr[sl], s, out=self.lrbuf[sl], mode=self.dmode)
+                if self.land:  # an LR pixel is NaN iff one of its taps is dry: fill, as inference does
+                    lrs = self.lrbuf[sl]
+                    call("srmi_tiles_fill", ptr(lrs), lrs.shape[0] * lrs.shape[1], lrs.shape[2], lrs.shape[3], None,
+                         torch.cuda.current_stream(self.device).cuda_stream)
                 eng.forward(self.params, self.lrbuf[sl], out=self.sr[sl])
-                if self.dy is not None:  # Charbonnier: the elementwise upstream gradient only
+                if self.dy is not None and not self.land:  # Charbonnier: the elementwise upstream gradient only
                     eng.charbonnier_partial(self.sr[sl], tgt[sl], None, count, CHARBONNIER_EPS, dy=self.dy[sl])
-                self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start)
+                self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start, lcparts)
                 if self.interp_loss:  # self.loss(btarget, binterp), dual_trainer.py:316-317
                     up = upsample(self.lrbuf[sl], s, out=self.up[sl], mode=self.umode)
                     itgt = hr[sl] if self.tgt_b is None else self.tgt_b[sl]
-                    self._loss_parts(itgt, up, iparts, t0 + sl.start)
+                    self._loss_parts(itgt, up, iparts, t0 + sl.start, icparts)
         for st in self.streams[1:]:
             main.wait_stream(st)
         self._reduce_losses(gb, count, icount)
         for st in self.streams[1:]:
             st.wait_stream(main)
+        if self.land:  # the upstream gradient from the finalised loss, zero on land
+            for k in range(self.micro):
+                sl = sls[k]
+                if sl.stop > sl.start:
+                    with self._ctx(k):
+                        call("srmi_loss_dy_masked", ptr(self.sr[sl]), ptr(tgt[sl]), self.sr[sl].numel(),
+                             self.loss_kind, CHARBONNIER_EPS, ptr(self.loss4), ptr(self.dy[sl]),
+                             torch.cuda.current_stream(self.device).cuda_stream)
         # backward per micro-batch with the global loss scale.  Data parallel: the
         # engines' gradients are added and all-reduced bucket by bucket as soon as every
         # engine is past the bucket, overlapped with the rest of backward
