@@ -51,6 +51,10 @@
  *                                   (NaN): masked statistics, a flood fill, a re-masking
  *                                   blend, a masked score.  No reference counterpart:
  *                                   the reference drops every tile that touches land.
+ *   srmi_spectra_workspace,
+ *   srmi_spectra                 -> windowed radial power spectra of a prediction against
+ *                                   a truth.  No reference counterpart: the reference
+ *                                   scores a field by its RMSE alone.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -523,6 +527,35 @@ int srmi_loss_from_parts_masked(const float* parts, const float* cparts, int nti
  * (float)(1 / loss4[1]), srmi_charbonnier_partial's dy. */
 int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int kind, float eps, const float* loss4,
                         float* dy, void* stream);
+
+/* ---- the spectral score (no reference counterpart) ---------------------- */
+/* Windowed (Welch) isotropic wavenumber spectra of a (prediction) and b (truth), both
+ * [C][H][W] fp32 on the device, possibly with NaN / Inf.
+ *   Windows: side P, a power of two in 16 .. 256 with P <= min(H, W); stride Q in 1 .. P on
+ *   both axes; origins min(i Q, L - P), i < srmi_overlap_count(L, P, Q), row-major.  A
+ *   window is skipped, for all channels, when any of its pixels is non-finite in a or in b
+ *   in any channel; nused = the windows not skipped.
+ *   Per used window and channel, for a and for b: subtract the window's mean (fp64 sum,
+ *   fp64 subtraction, rounded to fp32), multiply by the periodic Hann taper h(y) h(x),
+ *   h(p) = 0.5 - 0.5 cos(2 pi p / P), take the 2-D DFT Fa, Fb.  With W2 = sum (h(y) h(x))^2
+ *   the densities per bin are Eaa = |Fa|^2, Ebb = |Fb|^2, Eee = |Fa - Fb|^2 and
+ *   Cab = Re(Fa conj Fb), each / (P^2 W2): summed over ALL bins a density is the mean square
+ *   of the detrended, tapered window / mean((h h)^2) (Parseval).
+ *   Shells: signed wavenumbers ky, kx in [-P/2, P/2), shell j = floor(sqrt(ky^2 + kx^2) +
+ *   0.5); shells 0 .. P/2 are kept (K = P/2 + 1), the corner bins beyond are dropped.
+ * out [C][4][K] fp32 = the shell sums of Eaa, Ebb, Eee, Cab averaged over the used windows
+ * (nused == 0: NaN everywhere), nused one int32; both written by the device.  One complex
+ * fp32 FFT per window and channel serves both fields; shell sums and the average over
+ * windows are fp64 in a fixed order, no atomics: bit-identical from run to run.
+ * srmi_spectra_workspace (host only) gives the bytes of `workspace` (16-byte aligned; it
+ * need not be initialised): the skip flags, the [windows][C][4][K] fp64 partial sums and,
+ * for P >= 128, one P x P complex plane per launched workgroup (at most 512, whatever the
+ * window count).  No host synchronisation, no allocation: capturable.  P not a power of
+ * two or outside 16 .. 256 or > min(H, W), Q outside 1 .. P, C < 1, a missing buffer or a
+ * workspace that is too small: SRMI_ERR_ARG, and nothing is launched. */
+int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
+int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
+                 size_t workspace_bytes, float* out, int* nused, void* stream);
 
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)

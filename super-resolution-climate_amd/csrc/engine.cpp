@@ -1608,6 +1608,15 @@ int srmi_tiles_fill(float* tiles, long long nplanes, int h, int w, int* passes, 
   return tiles_fill_launch(tiles, nplanes, h, w, passes, S_(stream));
 }
 
+int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes) {
+  return spectra_workspace(C, H, W, P, Q, bytes);
+}
+
+int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
+                 size_t workspace_bytes, float* out, int* nused, void* stream) {
+  return spectra_launch(a, b, C, H, W, P, Q, workspace, workspace_bytes, out, nused, S_(stream));
+}
+
 int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
                            const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
                            int* nwet, void* stream) {

@@ -315,6 +315,10 @@ int tiles_fill_launch(float* tiles, long long nplanes, int h, int w, int* passes
 int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
                              const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
                              int* nwet, hipStream_t st);
+// the spectral score: windowed radial power spectra of two fields (spectra.hip)
+int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
+int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
+                   float* out, int* nused, hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

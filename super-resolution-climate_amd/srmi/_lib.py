@@ -143,6 +143,8 @@ _SIGS = {
     "srmi_llc_block_mask": ([P, C.c_longlong, C.c_int, P, C.c_int, P], C.c_int),
     "srmi_llc_compact_map": ([P, C.c_longlong, C.c_int, P, C.c_int, P, P], C.c_int),
     "srmi_tiles_keep": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
+    "srmi_spectra_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_spectra": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, P, P, P], C.c_int),
     "srmi_tiles_gather_dev": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)

@@ -224,3 +224,54 @@ def load_inference_results(path: str) -> Tuple[Dict[str, Var], Dict[str, float]]
                 co = {ren.get(d, d): c for d, c in co.items()}
             out[n] = Var(dims, vals_, co, sc)
     return out, losses
+
+
+SPECTRA_QUANTITIES = ("power_pred", "power_truth", "power_error", "cross", "error_ratio", "power_ratio", "coherence")
+
+
+def save_spectra(path: str, spectra: Dict[str, object], window: int, varnames: Sequence[str]) -> str:
+    """One spectral score (the dict of srmi.spectra.SpectralScore.measure, e.g. one entry
+    of RegionSuperResolver.score_spectra's third result) as a netCDF-3 file, through the
+    same scipy writer: one float32 variable per quantity on ('channel', 'shell'), the
+    coordinate ``wavenumber`` on 'shell' (cycles per pixel), ``nused`` as one int32 (on 'one'),
+    and the attributes ``window`` and ``varnames`` (the channel names joined by ``,``, as
+    loss_keys is).  No reference counterpart."""
+    from scipy.io import netcdf_file
+    missing = [k for k in SPECTRA_QUANTITIES + ("wavenumber", "nused") if k not in spectra]
+    if missing:
+        raise ValueError(f"spectra lack {missing}")
+    K = int(window) // 2 + 1
+    wn = _np(spectra["wavenumber"]).astype(np.float32)
+    if wn.shape != (K,):
+        raise ValueError(f"wavenumber {wn.shape} for a window of {window}")
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.window = np.int32(window)
+        f.varnames = ",".join(str(v) for v in varnames)
+        f.createDimension("channel", len(varnames))
+        f.createDimension("shell", K)
+        wv = f.createVariable("wavenumber", np.float32, ("shell",))
+        wv[:] = wn
+        wv.units = "cycles per pixel"
+        f.createDimension("one", 1)  # scipy's writer cannot assign a 0-d variable
+        nv = f.createVariable("nused", np.int32, ("one",))
+        nv[:] = _np(spectra["nused"]).reshape(-1)[:1].astype(np.int32)
+        for q in SPECTRA_QUANTITIES:
+            a = np.ascontiguousarray(_np(spectra[q]).astype(np.float32))
+            if a.shape != (len(varnames), K):
+                raise ValueError(f"{q}: {a.shape} is not {(len(varnames), K)}")
+            dv = f.createVariable(q, np.float32, ("channel", "shell"))
+            dv._FillValue = np.array([np.nan], dtype=np.float32)
+            dv[:] = a
+    return path
+
+
+def load_spectra(path: str) -> Tuple[Dict[str, np.ndarray], int, List[str]]:
+    """The inverse of save_spectra: (spectra as numpy arrays, window, varnames)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        out = {q: np.array(f.variables[q][:], dtype=np.float32) for q in SPECTRA_QUANTITIES + ("wavenumber",)}
+        out["nused"] = np.array(f.variables["nused"][:], dtype=np.int32).reshape(1)
+        return out, int(f.window), names.split(",") if names else []

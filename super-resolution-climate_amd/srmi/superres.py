@@ -13,7 +13,8 @@ alone with zero padding, disagree along every seam.
 [C, s h, s w] field: the LR region is cut into overlapping tiles
 (``srmi_region_to_tiles_overlap``), the tiles go through the inference engine, and the
 outputs are blended with a feathered window (``srmi_tiles_blend``) -- full coverage,
-all on the device.
+all on the device.  ``score`` gives the result one number, its RMSE against a truth;
+``score_spectra`` adds the windowed radial power spectra of srmi.spectra.
 
 The plan
 --------
@@ -218,6 +219,7 @@ class RegionSuperResolver:
         self.loss_m = torch.zeros(4, **f32)
         self.loss_i = torch.zeros(4, **f32)
         self._graph = None
+        self._spectra = {}  # (window, stride) -> the SpectralScore of each image (score_spectra)
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -333,6 +335,31 @@ class RegionSuperResolver:
         if self.land:
             losses["count"] = self.loss_m[1:2]
         return images, losses
+
+    def score_spectra(self, hr_region: torch.Tensor, window: int = 256, stride: Optional[int] = None):
+        """``score``, then the spectral score (srmi.spectra.SpectralScore) of 'model' and of
+        'interpolated' against hr_region: (images, losses, {'model': ..., 'interpolated':
+        ...}), each entry the dict of SpectralScore.measure -- the windowed radial spectra
+        of the image, of the truth and of their difference, the coherence, and the ratios
+        from which srmi.spectra.effective_resolution reads the wavelength down to which an
+        image beats the truth's variance.  window: the side in HR pixels, a power of two in
+        16 .. 256; stride: window // 2 when None.  images and losses are ``score``'s, bit for
+        bit; the spectra are views valid until the next call with the same window and
+        stride.  No host synchronisation.  With graph=True the spectra are measured after
+        the replay, outside the captured graph.
+
+        land=True: a window that touches a NaN of the image or of hr_region is skipped
+        ('nused' counts the rest), so a coast costs every window it crosses.  Filling the
+        land before the transform is out of scope here."""
+        from .spectra import SpectralScore
+        s = self.s
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        key = (int(window), None if stride is None else int(stride))
+        if key not in self._spectra:
+            self._spectra[key] = {name: SpectralScore((self.C, self.h * s, self.w * s), window, stride,
+                                                      device=self.device) for name in ("model", "interpolated")}
+        return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._spectra[key].items()}
 
     def set_params(self, params: torch.Tensor) -> None:
         """Load new weights: copied into the parameter buffer the engines (and the

@@ -24,6 +24,16 @@ Reports the HR MPix/s of all four, the ratio land on / land off per pair of wind
 (median and spread) with and without land, the share of the wet HR pixels each delivers
 finite, and the eager time of the three pieces land mode adds or replaces (cut, baseline,
 blends); writes profiles/superres_land_bench.json.
+
+--spectra [WINDOW]: what does the spectral score cost?  One RegionSuperResolver at the last
+of --overlaps scores a synthetic HR truth: ``score`` and ``score_spectra`` (window WINDOW,
+default 256, stride WINDOW / 2) alternate window by window, and the spectral stage alone
+(SpectralScore.measure of 'model' and of 'interpolated' against the truth) is timed in a
+window of its own.  Reports the median and the spread of each, the stage's share of the
+``score_spectra`` call, nused, the effective resolution of both images, and -- the only
+baseline there is -- the time of the numpy oracle (tests/spectra_oracle.py, fp64) on the
+host for the same two pairs of fields, run once, with the device's largest deviation from
+it; writes profiles/spectra_bench.json.
 """
 import argparse
 import json
@@ -129,6 +139,74 @@ def land_main(a, spec, params, lr, dev, kw):
     return res
 
 
+def spectra_main(a, spec, params, dev, kw):
+    import time
+
+    import numpy as np
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.spectra import effective_resolution
+    from srmi.superres import RegionSuperResolver
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import spectra_oracle as so
+    r, s, P = a.overlaps[-1], spec.scale, a.spectra
+    hr = torch.tensor(synthetic_hr(1, 1, a.side * s, 98)[0]).to(dev)
+    rs = RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                             graph=not a.no_graph, **kw)
+    for _ in range(a.warmup):
+        images, losses, spectra = rs.score_spectra(hr, window=P)
+    torch.cuda.synchronize()
+    scorers = rs._spectra[(P, None)]
+
+    def stage():
+        for name, sc in scorers.items():
+            sc.measure(images[name], hr)
+
+    runs = {"score": lambda: rs.score(hr), "score_spectra": lambda: rs.score_spectra(hr, window=P), "stage": stage}
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(a.regions):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.regions)
+    images, losses, spectra = rs.score_spectra(hr, window=P)
+    torch.cuda.synchronize()
+    truth = hr.cpu().numpy()
+    host, dev_err = 0.0, {}
+    for name in ("model", "interpolated"):
+        img = images[name].cpu().numpy()
+        t0 = time.perf_counter()
+        o64, n64 = so.spectra(img, truth, P, P // 2)
+        host += time.perf_counter() - t0
+        got = scorers[name].out.cpu().numpy().astype(np.float64)
+        dev_err[name] = float((np.abs(got - o64) / (o64[:, 0] + o64[:, 1])[:, None]).max())
+        if int(spectra[name]["nused"].item()) != n64:
+            raise SystemExit(f"superres_bench: {name}: nused {int(spectra[name]['nused'].item())} != oracle {n64}")
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    sc0 = scorers["model"]
+    res = {"tool": "superres_bench --spectra", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 score_spectra, 1 var, {a.side}^2 LR region -> {a.side * s}^2 HR, LR "
+                                  f"tile {a.tile}, overlap {r}; two spectral scores (model, interpolated) per call",
+                      "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                      "regions_per_window": a.regions, "window": P, "stride": sc0.stride,
+                      "windows": int(so.origins(a.side * s, P, sc0.stride).size) ** 2,
+                      "workspace_mib_per_score": round(sc0.workspace.numel() / 2 ** 20, 1)},
+           "ms": {k: {"median": round(med[k], 3), "min_max": [round(min(v), 3), round(max(v), 3)]}
+                  for k, v in ms.items()},
+           "stage_share_of_score_spectra": round(med["stage"] / med["score_spectra"], 4),
+           "score_spectra_over_score": round(med["score_spectra"] / med["score"], 4),
+           "nused": int(spectra["model"]["nused"].item()),
+           "effective_resolution_px": {k: effective_resolution(spectra[k]["error_ratio"], P)
+                                       for k in ("model", "interpolated")},
+           "host_oracle_fp64_s": round(host, 2),
+           "device_vs_oracle_max_rel": {k: float(f"{v:.3e}") for k, v in dev_err.items()}}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=1024, help="LR region side")
@@ -141,12 +219,18 @@ def main():
     ap.add_argument("--max-batch", type=int, default=None, help="RegionSuperResolver(max_batch=...); default: its own")
     ap.add_argument("--land", type=float, default=None, metavar="FRACTION",
                     help="paint a coast with about this share of dry pixels and compare land=True with land=False")
-    ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json)")
+    ap.add_argument("--spectra", type=int, nargs="?", const=256, default=None, metavar="WINDOW",
+                    help="time score_spectra's spectral stage at this window (default 256) beside score")
+    ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
+                                                "spectra_bench.json)")
     a = ap.parse_args()
+    if a.land is not None and a.spectra is not None:
+        raise SystemExit("superres_bench: --land and --spectra are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else "superres_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
+                             "spectra_bench.json" if a.spectra is not None else "superres_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("superres_bench: no GPU (there is no CPU path to time)")
     from oracle.rcan_oracle import synthetic_hr
@@ -162,8 +246,9 @@ def main():
     default_init_(params, table, 0)
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
-    if a.land is not None:
-        line = json.dumps(land_main(a, spec, params, lr, dev, kw))
+    if a.land is not None or a.spectra is not None:
+        line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
+                          spectra_main(a, spec, params, dev, kw))
         print(line)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
