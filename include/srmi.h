@@ -55,6 +55,12 @@
  *   srmi_spectra                 -> windowed radial power spectra of a prediction against
  *                                   a truth.  No reference counterpart: the reference
  *                                   scores a field by its RMSE alone.
+ *   srmi_spectral_loss_workspace,
+ *   srmi_spectral_loss_parts,
+ *   srmi_spectral_loss_from_parts,
+ *   srmi_spectral_loss_dy        -> a Fourier-amplitude term beside the pixel loss of a
+ *                                   training step.  No reference counterpart: the
+ *                                   reference trains on a pixel loss alone.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -556,6 +562,52 @@ int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int ki
 int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
 int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
                  size_t workspace_bytes, float* out, int* nused, void* stream);
+
+/* ---- the spectral loss term (no reference counterpart) ------------------ */
+/* A Fourier-space term beside the pixel loss of a training step: the windowed amplitudes
+ * of the error of pred against target, both [nplanes][H][W] fp32 on the device (nplanes =
+ * N C), possibly with NaN / Inf.
+ *   Jobs: windows of side P in {16, 32, 64}, P <= min(H, W), stride Q in 1 .. P, origins
+ *   min(i Q, L - P), i < srmi_overlap_count(L, P, Q), row-major, nwin per plane.  A job is one
+ *   window of one plane; it is skipped when any of its P^2 pixels is non-finite in pred or
+ *   in target (per plane, not across channels).
+ *   Per used job: d = pred - target (fp32), z = h(y) h(x) d with the periodic Hann taper
+ *   h(q) = 0.5 - 0.5 cos(2 pi q / P) (the mean is NOT removed), D = DFT2(z), unnormalised;
+ *   c = P^2 W2, W2 = sum (h(y) h(x))^2; A_k = sqrt(|D_k|^2 / c + eps) for each of the P^2
+ *   bins.  S = the sum of A_k over the bins of the used jobs, Nused = the used jobs, and
+ *   L_spec = S / (Nused P); Nused = 0: L_spec = 0 and its gradient is 0.
+ *   Gradient: with G_k = D_k / (c A_k) (Hermitian), d L_spec / d pred (y, x) =
+ *   1 / (Nused P) * the sum over the used jobs w covering (y, x) of h(y - y0_w) h(x - x0_w)
+ *   Re IDFT2(G) (y - y0_w, x - x0_w), the inverse unnormalised.  The taper is 0 at q = 0: a
+ *   plane's first row and column get no spectral gradient.
+ * Arithmetic: fp32 transforms (two jobs of a plane share one complex transform), the bins
+ * and every sum in fp64 in a fixed order, no atomics: bit-identical from run to run, and
+ * the same bits whether the planes go through one call or several.
+ * srmi_spectral_loss_workspace (host only): the bytes of `workspace` (16-byte aligned,
+ * need not be initialised) for nplanes planes; it is laid out plane by plane, bytes /
+ * nplanes each, so a call over planes p0 .. p0 + n - 1 of a batch takes the batch's
+ * workspace + p0 * (bytes / nplanes).
+ * srmi_spectral_loss_parts: per plane the job sums added in window order (fp64, rounded
+ * once) into parts[nplanes] and the used jobs into cparts[nplanes] (floats, exact); the
+ * gradient windows of the used jobs, tapered and not yet scaled, and the used flags stay
+ * in the workspace for srmi_spectral_loss_dy.
+ * srmi_spectral_loss_from_parts: parts and cparts summed over the nplanes of the (global)
+ * batch in a fixed order, spec4 = {S, Nused, 1 / (Nused P), L_spec} (all 0 when Nused = 0)
+ * and total[0] = fma(weight, spec4[3], loss4[3]); loss4 (a finalised pixel loss) is only read.
+ * srmi_spectral_loss_dy: dy [nplanes][H][W] = fma(weight * spec4[2], the fp32 sum of the used
+ * windows' gradients covering the pixel in ascending window index, dy); the scale is read
+ * from the device.  A pixel no used window covers is not written; weight == 0 launches nothing.
+ * All three: no allocation, no host read, capturable.  SRMI_ERR_ARG, nothing launched: P
+ * not 16, 32 or 64 or > min(H, W); Q outside 1 .. P; nplanes < 1; eps <= 0; weight < 0 or
+ * not finite; a missing buffer; a workspace that is too small or not 16-byte aligned. */
+int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
+int srmi_spectral_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
+                             float eps, float* parts, float* cparts, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
+                                  const float* loss4, float* spec4, float* total, void* stream);
+int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long long nplanes, int H, int W, int P, int Q,
+                          float weight, const float* spec4, float* dy, void* stream);
 
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)

@@ -1617,6 +1617,27 @@ int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int
   return spectra_launch(a, b, C, H, W, P, Q, workspace, workspace_bytes, out, nused, S_(stream));
 }
 
+int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
+  return spectral_loss_workspace(nplanes, H, W, P, Q, bytes);
+}
+
+int srmi_spectral_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
+                             float eps, float* parts, float* cparts, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  return spectral_loss_parts_launch(pred, target, nplanes, H, W, P, Q, eps, parts, cparts, workspace, workspace_bytes,
+                                    S_(stream));
+}
+
+int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
+                                  const float* loss4, float* spec4, float* total, void* stream) {
+  return spectral_loss_from_parts_launch(parts, cparts, nplanes, P, weight, loss4, spec4, total, S_(stream));
+}
+
+int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long long nplanes, int H, int W, int P, int Q,
+                          float weight, const float* spec4, float* dy, void* stream) {
+  return spectral_loss_dy_launch(workspace, workspace_bytes, nplanes, H, W, P, Q, weight, spec4, dy, S_(stream));
+}
+
 int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
                            const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
                            int* nwet, void* stream) {

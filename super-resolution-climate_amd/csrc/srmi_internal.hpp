@@ -319,6 +319,14 @@ int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int fl
 int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
 int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
                    float* out, int* nused, hipStream_t st);
+// the spectral loss term of the training step (spectral_loss.hip)
+int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
+int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
+                               float eps, float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st);
+int spectral_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, int P, float weight,
+                                    const float* loss4, float* spec4, float* total, hipStream_t st);
+int spectral_loss_dy_launch(const void* ws, size_t ws_bytes, long long nplanes, int H, int W, int P, int Q,
+                            float weight, const float* spec4, float* dy, hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

@@ -145,6 +145,13 @@ _SIGS = {
     "srmi_tiles_keep": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_spectra_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_spectra": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, P, P, P], C.c_int),
+    "srmi_spectral_loss_workspace": ([C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)],
+                                     C.c_int),
+    "srmi_spectral_loss_parts": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P, P, P,
+                                  C.c_size_t, P], C.c_int),
+    "srmi_spectral_loss_from_parts": ([P, P, C.c_longlong, C.c_int, C.c_float, P, P, P, P], C.c_int),
+    "srmi_spectral_loss_dy": ([P, C.c_size_t, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P, P, P],
+                              C.c_int),
     "srmi_tiles_gather_dev": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)

@@ -19,7 +19,7 @@ gradients are all-reduced as described in srmi/dist.py.
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
@@ -28,6 +28,7 @@ from ._lib import SRMI_LOSS_MEAN, SRMI_LOSS_RMSE, TILE_LOSS_SUB, call, ptr
 from .config import check_fused_task, data_downsample_factor, interp_mode
 from .dist import DistInfo, GradReducer, allreduce_sum_
 from .engine import Engine, NetSpec, adam_step, axpy, downsample, engine_stream, interp_size, upsample
+from .spectra import SpectralLoss, check_spectral_loss_config
 
 LOSS_KINDS = {"l2": SRMI_LOSS_RMSE, "charbonnier": SRMI_LOSS_MEAN}
 CHARBONNIER_EPS = 1e-6  # ModelTrainer.eps, sres/controller/dual_trainer.py:122
@@ -71,7 +72,7 @@ class FusedTrainer:
                  info: Optional[DistInfo] = None, device: Optional[torch.device] = None, seed: int = 0,
                  params: Optional[torch.Tensor] = None, micro: Optional[int] = None, loss_fn: str = "l2",
                  cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
-                 land: bool = False):
+                 land: bool = False, spectral: Optional[Mapping] = None):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -92,7 +93,15 @@ class FusedTrainer:
         over the elements where prediction and target are both finite
         (srmi_tile_loss_parts_masked, the count summed on the device), and the backward
         runs from an upstream gradient that is zero on land (srmi_loss_dy_masked) for
-        both loss functions.  Refused with task.data_downsample > 1."""
+        both loss functions.  Refused with task.data_downsample > 1.
+        spectral (no reference counterpart; DESIGN.md §1 "Spectral loss"): None, or the
+        configuration of a spectral loss term, dict(weight=1.0, window=64, stride=32,
+        eps=1e-12) (srmi.spectra.SpectralLoss's arguments; a missing key takes that
+        default).  The step's loss is then loss_fn + weight * L_spec, L_spec the windowed
+        Fourier amplitudes of sr - target over the global batch, and the backward runs from
+        the sum of both upstream gradients.  Windows that touch a non-finite pixel are
+        skipped, so land=True needs nothing more.  A bad window, stride, weight (finite,
+        >= 0) or eps raises ValueError here."""
         if loss_fn not in LOSS_KINDS:  # single_product_loss, dual_trainer.py:210-211
             raise ValueError(f"Unknown single-product loss function {loss_fn}")
         if task is None:
@@ -111,6 +120,19 @@ class FusedTrainer:
                              f"{spec.nchannels_in}-channel interpolated input does not broadcast (as in the reference)")
         self.loss_fn = loss_fn
         self.loss_kind = LOSS_KINDS[loss_fn]
+        spectral_cfg = None
+        if spectral is not None:
+            if not isinstance(spectral, Mapping):
+                raise ValueError(f"spectral: a dict(weight=, window=, stride=, eps=) or None, got {spectral!r}")
+            extra = set(spectral) - {"weight", "window", "stride", "eps"}
+            if extra:
+                raise ValueError(f"spectral: unknown keys {sorted(extra)}")
+            P, Q, seps, sw = check_spectral_loss_config(spectral.get("window", 64), spectral.get("stride", 32),
+                                                        spectral.get("eps", 1e-12), spectral.get("weight", 1.0))
+            if P > min(lr_hw) * spec.scale:
+                raise ValueError(f"spectral loss window {P} larger than the HR tile "
+                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
+            spectral_cfg = dict(window=P, stride=Q, eps=seps, weight=sw)
         self.info = info or DistInfo()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.tindx = None if tindx is None else torch.tensor(tindx, dtype=torch.long, device=self.device)
@@ -150,7 +172,9 @@ class FusedTrainer:
                    if interp_loss else None)
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
         # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
-        self.dy = torch.empty_like(self.sr) if self.loss_kind == SRMI_LOSS_MEAN or self.land else None
+        # (a spectral term: always -- its gradient is added to the pixel loss's)
+        self.dy = (torch.empty_like(self.sr)
+                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None else None)
         # the selected target channels (index_select) and, for the interp metric, that
         # target broadcast over the input's channels (1-channel target, :316-317)
         self.tgt = torch.empty_like(self.sr) if self.tindx is not None else None
@@ -173,6 +197,10 @@ class FusedTrainer:
         # through the same single all-reduce (whole numbers: x + 0 and their sums are exact)
         self.gparts = torch.zeros((4 if self.land else 2) * self.gcap * TILE_LOSS_SUB, dtype=torch.float32,
                                   device=self.device)
+        # the spectral term: the gradient windows of this rank's tiles, and the per-plane
+        # parts and used-window counts of the GLOBAL batch, which travel as gparts does
+        self.spectral = (SpectralLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **spectral_cfg)
+                         if spectral_cfg is not None else None)
         self.streams = [None] + [engine_stream(self.device) for _ in range(micro - 1)]
         self.dp_staged = not dp_reducer_stream
         self.reducer = GradReducer(self.eng.table, spec.arch, spec.nlayers, self.info, self.device,
@@ -283,6 +311,11 @@ class FusedTrainer:
             lcparts, icparts = self.gparts[m * n:m * n + n], self.gparts[m * n + n:m * n + 2 * n]
         if self.info.enabled:  # the other ranks' tiles' parts stay 0 here
             self.gparts[:(4 if self.land else 2) * n].zero_()
+        if self.spectral is not None:
+            self.spectral.set_global_batch(gb)
+            if self.info.enabled:
+                for v in self.spectral.views():
+                    v.zero_()
         for st in self.streams[1:]:
             st.wait_stream(main)
         # forward + loss partials per micro-batch (an empty micro-batch adds nothing)
@@ -300,6 +333,8 @@ class FusedTrainer:
                 if self.dy is not None and not self.land:  # Charbonnier: the elementwise upstream gradient only
                     eng.charbonnier_partial(self.sr[sl], tgt[sl], None, count, CHARBONNIER_EPS, dy=self.dy[sl])
                 self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start, lcparts)
+                if self.spectral is not None:
+                    self.spectral.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
                 if self.interp_loss:  # self.loss(btarget, binterp), dual_trainer.py:316-317
                     up = upsample(self.lrbuf[sl], s, out=self.up[sl], mode=self.umode)
                     itgt = hr[sl] if self.tgt_b is None else self.tgt_b[sl]
@@ -307,9 +342,15 @@ class FusedTrainer:
         for st in self.streams[1:]:
             main.wait_stream(st)
         self._reduce_losses(gb, count, icount)
+        if self.spectral is not None:  # the term and its scale from the global batch's parts and counts
+            if self.info.enabled:
+                allreduce_sum_(self.spectral.gparts[:2 * gb * self.spectral.C], self.info)
+            self.spectral.finalize(self.loss4)
         for st in self.streams[1:]:
             st.wait_stream(main)
-        if self.land:  # the upstream gradient from the finalised loss, zero on land
+        # the upstream gradient from the finalised loss, zero on land; with a spectral term
+        # the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then the term's on top
+        if self.land or (self.spectral is not None and self.loss_kind == SRMI_LOSS_RMSE):
             for k in range(self.micro):
                 sl = sls[k]
                 if sl.stop > sl.start:
@@ -317,6 +358,12 @@ class FusedTrainer:
                         call("srmi_loss_dy_masked", ptr(self.sr[sl]), ptr(tgt[sl]), self.sr[sl].numel(),
                              self.loss_kind, CHARBONNIER_EPS, ptr(self.loss4), ptr(self.dy[sl]),
                              torch.cuda.current_stream(self.device).cuda_stream)
+        if self.spectral is not None:
+            for k in range(self.micro):
+                sl = sls[k]
+                if sl.stop > sl.start:
+                    with self._ctx(k):
+                        self.spectral.add_dy(self.dy[sl], rows=sl.start)
         # backward per micro-batch with the global loss scale.  Data parallel: the
         # engines' gradients are added and all-reduced bucket by bucket as soon as every
         # engine is past the bucket, overlapped with the rest of backward
@@ -396,6 +443,9 @@ class FusedTrainer:
                 eng.pack(self.params)
         for st in self.streams[1:]:
             main.wait_stream(st)
+        if self.spectral is not None:
+            return {"loss": self.spectral.total, "interp_loss": self.iloss4[3:4], "pixel_loss": self.loss4[3:4],
+                    "spectral_loss": self.spectral.spec4[3:4]}
         return {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
