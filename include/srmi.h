@@ -51,6 +51,11 @@
  *                                   (NaN): masked statistics, a flood fill, a re-masking
  *                                   blend, a masked score.  No reference counterpart:
  *                                   the reference drops every tile that touches land.
+ *   srmi_tiles_dihedral,
+ *   srmi_tiles_blend_ensemble    -> geometric self-ensemble of the overlapped tiles: the
+ *                                   dihedral variants of xyflip (batch.py:37-49), their
+ *                                   back-transformed mean and spread.  No reference
+ *                                   counterpart: the reference flips training batches only.
  *   srmi_spectra_workspace,
  *   srmi_spectra                 -> windowed radial power spectra of a prediction against
  *                                   a truth.  No reference counterpart: the reference
@@ -481,6 +486,47 @@ int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* d
  * is stored as a float: exact up to 2^24 elements. */
 int srmi_rmse_partial_masked(srmi_engine* e, const float* pred, const float* target, size_t n, float* loss4,
                              void* stream);
+
+/* ---- geometric self-ensemble (no reference counterpart) ------------------ */
+/* The "+" variant of the RCAN / EDSR papers: the model runs on dihedral variants of every
+ * tile, the outputs are transformed back and averaged, and their standard deviation is a
+ * per-pixel spread.  `variants` is a bit mask, 1 .. 255: bit f selects variant f of xyflip
+ * (sres/base/source/batch.py:37-49 -- bit 0 of f flips x, bit 1 flips y, bit 2 then swaps
+ * the axes), K = popcount(variants), and the selected variants are stored in ascending f. */
+/* in [nplanes][h][w] fp32 -> out [K][nplanes][h][w]: variant f at output pixel (y, x) is
+ * `in` at the source pixel srmi_batch_prep reads there (the same index map) -- in numpy
+ * terms flip x if bit 0, flip y if bit 1, then swap the last two axes if bit 2.  A pure
+ * permutation: every bit pattern is kept, NaN payloads and -0 included.  A 64 x 64 block
+ * of a source plane is read once, row by row, into LDS (padded pitch) and written once
+ * per variant, row by row: no lane walks a column of HBM.  The float4 form is taken where
+ * w % 4 == 0 and both buffers are 16-byte aligned, a scalar one otherwise.  A variant
+ * >= 4 with h != w, or nplanes, h, w < 1, or more than 2^31 - 1 blocks: SRMI_ERR_SHAPE;
+ * `variants` outside 1 .. 255, a missing buffer, or in == out: SRMI_ERR_ARG. */
+int srmi_tiles_dihedral(const float* in, long long nplanes, int h, int w, int variants, float* out, void* stream);
+/* tiles [K][ny*nx][C][Ty][Tx]: slab j holds the model outputs of variant f_j of every
+ * tile, still in the transformed frame; off / div / bad [ny*nx].. as for srmi_tiles_blend,
+ * shared by the variants.  Per output pixel (c, Y, X) and slab j, B_j is
+ * srmi_tiles_blend's value of the back-transformed slab (mask_src != NULL:
+ * srmi_tiles_blend_masked's, with `scale`; mask_src == NULL: scale is ignored), bit for
+ * bit: the same plan, cover, integer ramp, ascending (iy, ix) order, bad tiles skipped
+ * before any read, no cover -> canonical NaN, one cover -> a copy, one division.  The
+ * back-transformed slab is never materialised: for covering tile k and tile-local
+ * (qy, qx) the kernel reads slab j at (y, x) with a = (f & 2) ? Ty - 1 - qy : qy,
+ * b = (f & 1) ? Tx - 1 - qx : qx, (y, x) = (f & 4) ? (b, a) : (a, b).  Then, in fp32 and
+ * ascending j,
+ *   mean   [C][Ho][Wo] = (B_0 + ... + B_{K-1}) / (float)K
+ *   spread [C][Ho][Wo] = sqrtf(((B_0 - mean)^2 + ...) / (float)K)      (ddof 0; optional)
+ * Both sums add their terms pairwise in ascending j -- ((t0 + t1) + (t2 + t3)) + ((t4 + t5)
+ * + (t6 + t7)), the terms j >= K left out -- so K = 1, 2, 4 or 8 identical variants give
+ * mean == B_0 bit for bit and spread == +0 (a running sum rounds at 3 B, 5 B, 7 B).
+ * NaN propagates into both.  No atomics, deterministic.  A workgroup owns 16 rows x 64
+ * pixels of the output (quad form; 16 x 16 in the scalar form), so a wave's loads cover
+ * whole 64-byte segments of a slab whether or not its axes are swapped.  `variants`
+ * outside 1 .. 255: SRMI_ERR_ARG; a variant >= 4 with Ty != Tx: SRMI_ERR_SHAPE; otherwise
+ * the errors of srmi_tiles_blend (mask_src given: of srmi_tiles_blend_masked). */
+int srmi_tiles_blend_ensemble(const float* tiles, int variants, const float* off, const float* div, const int* bad,
+                              int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale,
+                              float* mean, float* spread, void* stream);
 
 /* ---- land in training (no reference counterpart: the reference drops every tile that
  * touches land, and its losses know no mask) ------------------------------------ */

@@ -1599,6 +1599,17 @@ int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* d
   return tiles_blend_masked_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, S_(stream));
 }
 
+int srmi_tiles_dihedral(const float* in, long long nplanes, int h, int w, int variants, float* out, void* stream) {
+  return tiles_dihedral_launch(in, nplanes, h, w, variants, out, S_(stream));
+}
+
+int srmi_tiles_blend_ensemble(const float* tiles, int variants, const float* off, const float* div, const int* bad,
+                              int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale,
+                              float* mean, float* spread, void* stream) {
+  return tiles_blend_ensemble_launch(tiles, variants, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, mean,
+                                     spread, S_(stream));
+}
+
 int srmi_tiles_dry(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
                    void* stream) {
   return tiles_dry_launch(region, C, H, W, ty, tx, min_wet, bad, nwet, S_(stream));

@@ -308,6 +308,11 @@ int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int
 int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
                               int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
                               hipStream_t st);
+// geometric self-ensemble: the dihedral variants of tile planes, the blend of their outputs (tiles.hip)
+int tiles_dihedral_launch(const float* in, long long nplanes, int h, int w, int variants, float* out, hipStream_t st);
+int tiles_blend_ensemble_launch(const float* tiles, int variants, const float* off, const float* dv, const int* bad,
+                                int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src,
+                                int scale, float* mean, float* spread, hipStream_t st);
 // land in training: the keep flags with a threshold, the fill in place, the masked prep
 int tiles_dry_launch(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
                      hipStream_t st);

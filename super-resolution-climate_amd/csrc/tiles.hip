@@ -25,6 +25,10 @@
 //
 // region_to_tiles_overlap / tiles_blend generalise the cut and the mosaic to overlapping
 // tiles and a feathered blend (srmi.superres).  The reference has no overlapped form.
+//
+// tiles_dihedral / tiles_blend_ensemble are the geometric self-ensemble of those tiles: the
+// xyflip variants (batch.py:37-49) of every tile plane, and the mean and spread of their
+// back-transformed, blended outputs.  The reference flips training batches only.
 #include <math.h>
 
 #include "common.hpp"
@@ -257,11 +261,16 @@ __device__ __forceinline__ double block_sum1024(double v, double* red) {
 // output pixel (y, x) of xyflip(...) reads source pixel (sy, sx) (square tiles):
 // swap (bit 2) first, then flip y (bit 1), then flip x (bit 0) -- the inverse of
 // the reference's flip-x, flip-y, transpose sequence.
-__device__ __forceinline__ void flip_src(int f, int T, int y, int x, int& sy, int& sx) {
+// The h x w form serves srmi_tiles_dihedral: the flips alone (f < 4) keep a rectangular
+// plane's shape, a swap needs h == w.
+__device__ __forceinline__ void flip_src(int f, int h, int w, int y, int x, int& sy, int& sx) {
   sy = (f & 4) ? x : y;
   sx = (f & 4) ? y : x;
-  if (f & 2) sy = T - 1 - sy;
-  if (f & 1) sx = T - 1 - sx;
+  if (f & 2) sy = h - 1 - sy;
+  if (f & 1) sx = w - 1 - sx;
+}
+__device__ __forceinline__ void flip_src(int f, int T, int y, int x, int& sy, int& sx) {
+  flip_src(f, T, T, y, x, sy, sx);
 }
 
 template <bool kLds>
@@ -673,6 +682,9 @@ __device__ __forceinline__ void overlap_cover(int p, int L, int t, int S, int n,
 // R = t - S, so two regularly overlapping tiles weigh (R - q) / (R + 1) and (q + 1) /
 // (R + 1) across their overlap (never zero), and R = 0 weighs everything 1
 __device__ __forceinline__ int overlap_weight(int q, int t, int R) { return min(min(q + 1, t - q), R + 1); }
+// the de-normalisation of a tile value, one expression for tiles_blend_kernel and
+// tiles_blend_ensemble_kernel: whatever the compiler makes of it, it makes in both
+__device__ __forceinline__ float blend_denorm(float x, float sd, float m) { return x * sd + m; }
 
 // out[c][Y][X] = sum_k w_k v_k / sum_k w_k over the non-bad tiles k covering (Y, X), v =
 // tile value * div + off (off == NULL: as stored), w = wy wx.  Gather form: a thread owns
@@ -736,7 +748,7 @@ __global__ void __launch_bounds__(256) tiles_blend_kernel(const float* __restric
       if (off) {
         const float sd = dv[p], m = off[p];
 #pragma unroll
-        for (int e = 0; e < kV; ++e) v[e] = v[e] * sd + m;
+        for (int e = 0; e < kV; ++e) v[e] = blend_denorm(v[e], sd, m);
       }
       ++cnt;
 #pragma unroll
@@ -796,6 +808,285 @@ int tiles_blend_masked_launch(const float* tiles, const float* off, const float*
                               hipStream_t st) {
   if (!mask_src || scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale) return SRMI_ERR_ARG;
   return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, st);
+}
+
+// ------------------------------------------------ geometric self-ensemble (the "+" variant)
+// No reference counterpart.  The model runs on the dihedral variants of every tile --
+// variant f is xyflip's (flip_src above: bit 0 flips x, bit 1 flips y, bit 2 swaps the
+// axes), a bit mask selects which, stored in ascending f -- and the blend averages the
+// back-transformed outputs and takes their spread.
+//
+// tiles_dihedral: in [nplanes][h][w] -> out [K][nplanes][h][w], a pure permutation.  One
+// workgroup owns one 64 x 64 block of one SOURCE plane: the block is read from HBM once,
+// row by row, into LDS with a padded pitch (65: the column walks of the swapping variants
+// hit distinct banks), and written once per variant to where that variant puts it, row by
+// row again -- no lane walks a column of HBM.  The plane index shares grid.x with the
+// blocks (a region's K n C planes do not fit grid.y).
+constexpr int kDihB = 64, kDihP = kDihB + 1;
+
+template <bool kVec>
+__global__ void __launch_bounds__(256) tiles_dihedral_kernel(const float* __restrict__ in, int h, int w, int nby,
+                                                             int nbx, int variants, size_t slab,
+                                                             float* __restrict__ out) {
+  __shared__ float blk[kDihB * kDihP];
+  const int bid = (int)blockIdx.x, tid = threadIdx.x;
+  const int bx = bid % nbx, by = (bid / nbx) % nby;
+  const size_t plane = (size_t)(bid / (nbx * nby)) * h * w;
+  const int y0 = by * kDihB, x0 = bx * kDihB;
+  const int bh = min(kDihB, h - y0), bw = min(kDihB, w - x0);
+  const float* src = in + plane;
+  if (kVec) {  // w % 4 == 0: x0 and bw are multiples of 4
+    const int bw4 = bw >> 2;
+    for (int i = tid; i < bh * bw4; i += 256) {
+      const int r = i / bw4, q = i - r * bw4;
+      const float4 v = *reinterpret_cast<const float4*>(src + (size_t)(y0 + r) * w + x0 + 4 * q);
+      float* d = blk + r * kDihP + 4 * q;
+      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+  } else {
+    for (int i = tid; i < bh * bw; i += 256) {
+      const int r = i / bw, q = i - r * bw;
+      blk[r * kDihP + q] = src[(size_t)(y0 + r) * w + x0 + q];
+    }
+  }
+  __syncthreads();
+  int j = 0;
+  for (int rem = variants; rem; rem &= rem - 1, ++j) {
+    const int f = __ffs(rem) - 1;
+    // where the block lands: the inverse of flip_src on its corner (a swap has h == w)
+    const int a0 = (f & 2) ? h - y0 - bh : y0, b0 = (f & 1) ? w - x0 - bw : x0;
+    const int oy0 = (f & 4) ? b0 : a0, ox0 = (f & 4) ? a0 : b0;
+    const int oh = (f & 4) ? bw : bh, ow = (f & 4) ? bh : bw;
+    float* dst = out + (size_t)j * slab + plane;
+    if (kVec) {  // h == w for a swap, so ox0 and ow are multiples of 4 there too
+      const int ow4 = ow >> 2;
+      for (int i = tid; i < oh * ow4; i += 256) {
+        const int r = i / ow4, q = i - r * ow4;
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          int sy, sx;
+          flip_src(f, h, w, oy0 + r, ox0 + 4 * q + e, sy, sx);
+          o[e] = blk[(sy - y0) * kDihP + (sx - x0)];
+        }
+        *reinterpret_cast<float4*>(dst + (size_t)(oy0 + r) * w + ox0 + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+      }
+    } else {
+      for (int i = tid; i < oh * ow; i += 256) {
+        const int r = i / ow, q = i - r * ow;
+        int sy, sx;
+        flip_src(f, h, w, oy0 + r, ox0 + q, sy, sx);
+        dst[(size_t)(oy0 + r) * w + ox0 + q] = blk[(sy - y0) * kDihP + (sx - x0)];
+      }
+    }
+  }
+}
+
+int tiles_dihedral_launch(const float* in, long long nplanes, int h, int w, int variants, float* out,
+                          hipStream_t st) {
+  if (variants < 1 || variants > 255 || !in || !out || in == out) return SRMI_ERR_ARG;
+  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
+  if ((variants & 0xf0) && h != w) return SRMI_ERR_SHAPE;  // a swap of a rectangular plane
+  const int nby = (h + kDihB - 1) / kDihB, nbx = (w + kDihB - 1) / kDihB;
+  if (nplanes * nby * nbx > 0x7fffffffLL) return SRMI_ERR_SHAPE;  // grid.x
+  const size_t slab = (size_t)nplanes * h * w;
+  const dim3 grid((unsigned)(nplanes * nby * nbx));
+  if (w % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL(tiles_dihedral_kernel<true>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
+  else
+    hipLaunchKernelGGL(tiles_dihedral_kernel<false>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// kV values of slab `s` ([Ty][Tx], stored in variant f's frame) at tile-local (qy, qx ..
+// qx + kV - 1) of the back-transformed tile: the inverse of flip_src.  kV == 4 (qx, Tx
+// multiples of 4): one float4 for the variants that keep the axes (reversed where x is
+// flipped), four reads down one column for those that swap them.
+template <int kV>
+__device__ __forceinline__ void ensemble_read(const float* __restrict__ s, int f, int Ty, int Tx, int qy, int qx,
+                                              float (&v)[kV]) {
+  const int a = (f & 2) ? Ty - 1 - qy : qy;
+  if (f & 4) {  // (y, x) = (b, a), Ty == Tx
+#pragma unroll
+    for (int e = 0; e < kV; ++e) {
+      const int b = (f & 1) ? Tx - 1 - (qx + e) : qx + e;
+      v[e] = s[(size_t)b * Tx + a];
+    }
+  } else if constexpr (kV == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(s + (size_t)a * Tx + ((f & 1) ? Tx - 4 - qx : qx));
+    if (f & 1) {
+      v[0] = q.w; v[1] = q.z; v[2] = q.y; v[3] = q.x;
+    } else {
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+  } else {
+    v[0] = s[(size_t)a * Tx + ((f & 1) ? Tx - 1 - qx : qx)];
+  }
+}
+
+// a[0] + .. + a[K - 1] in fp32, ascending j, added pairwise: ((a0 + a1) + (a2 + a3)) +
+// ((a4 + a5) + (a6 + a7)) with the terms j >= K left out (not added as zeros: -0 stays -0).
+// K equal values then sum to K times the value exactly for K = 1, 2, 4, 8, so identical
+// variants average to themselves bit for bit (a running sum rounds at 3 x, 5 x, 7 x).
+__device__ __forceinline__ float ensemble_sum(const float (&a)[8], int K) {
+  const float s01 = K > 1 ? __fadd_rn(a[0], a[1]) : a[0], s23 = K > 3 ? __fadd_rn(a[2], a[3]) : a[2];
+  const float s45 = K > 5 ? __fadd_rn(a[4], a[5]) : a[4], s67 = K > 7 ? __fadd_rn(a[6], a[7]) : a[6];
+  const float s03 = K > 2 ? __fadd_rn(s01, s23) : s01, s47 = K > 6 ? __fadd_rn(s45, s67) : s45;
+  return K > 4 ? __fadd_rn(s03, s47) : s03;
+}
+
+// tiles [K][ny*nx][C][Ty][Tx]: per output pixel and slab j the value B_j of
+// tiles_blend_kernel on the back-transformed slab -- the same cover, weights, order, fmaf
+// chain, copy at one cover and division, the read address alone differs -- then in fp32
+// (ensemble_sum) mean = (B_0 + ...) / K and spread = sqrtf(((B_0 - mean)^2 + ...) / K).  The
+// covering tiles are the outer loop (weights, bad flags, off and div are shared by the
+// variants), the K slabs the inner one; the K accumulators live in registers.
+// A workgroup owns 16 output rows x 16 kV pixels.  kV == 4: a wave is all 16 rows of four
+// neighbouring quads (lane = row + 16 quad), so a load of a slab that keeps the axes
+// covers 16 rows x 64 bytes and each of the four column reads of a swapped slab 4 rows x
+// 64 bytes -- whole 64-byte segments either way, where the row-per-workgroup footprint of
+// tiles_blend_kernel would walk a swapped slab as 64 dwords a row pitch apart.  kV == 1:
+// a wave is 8 x 8 pixels, 32-byte runs for both kinds.
+// grid (ceil(Wo / kV / 16), ceil(Ho / 16), C)
+template <int kV, bool kMask>
+__global__ void __launch_bounds__(256) tiles_blend_ensemble_kernel(
+    const float* __restrict__ tiles, int variants, int K, const float* __restrict__ off, const float* __restrict__ dv,
+    const int* __restrict__ bad, int C, int Ty, int Tx, int Sy, int Sx, int ny, int nx, int Ho, int Wo,
+    const float* __restrict__ mask_src, int scale, float* __restrict__ mean, float* __restrict__ spread) {
+  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int ly = kV == 4 ? (l & 15) : 8 * (wv >> 1) + (l & 7);
+  const int lx = kV == 4 ? 4 * wv + (l >> 4) : 8 * (wv & 1) + (l >> 3);
+  const int X = (blockIdx.x * 16 + lx) * kV, Y = blockIdx.y * 16 + ly, c = blockIdx.z;
+  if (X >= Wo || Y >= Ho) return;
+  const float nan = __int_as_float(0x7fc00000);
+  const size_t o = ((size_t)c * Ho + Y) * Wo + X;
+  if constexpr (kMask) {
+    if (!isfinite(mask_src[((size_t)c * (Ho / scale) + Y / scale) * (Wo / scale) + X / scale])) {
+      if constexpr (kV == 4) {
+        *reinterpret_cast<float4*>(mean + o) = make_float4(nan, nan, nan, nan);
+        if (spread) *reinterpret_cast<float4*>(spread + o) = make_float4(nan, nan, nan, nan);
+      } else {
+        mean[o] = nan;
+        if (spread) spread[o] = nan;
+      }
+      return;
+    }
+  }
+  const int Ry = Ty - Sy, Rx = Tx - Sx;
+  const size_t slab = (size_t)ny * nx * C * Ty * Tx;
+  int ylo, yhi, xlo, xhi;
+  overlap_cover(Y, Ho, Ty, Sy, ny, ylo, yhi);
+  overlap_cover(X, Wo, Tx, Sx, nx, xlo, xhi);
+  float acc[8][kV], one[8][kV];
+  int wsum[kV], cnt = 0;
+#pragma unroll
+  for (int e = 0; e < kV; ++e) wsum[e] = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+#pragma unroll
+    for (int e = 0; e < kV; ++e) {
+      acc[j][e] = 0.f;
+      one[j][e] = 0.f;
+    }
+  }
+  for (int iy = ylo; iy <= yhi; ++iy) {
+    const int qy = Y - min(iy * Sy, Ho - Ty);
+    const int wy = overlap_weight(qy, Ty, Ry);
+    for (int ix = xlo; ix <= xhi; ++ix) {
+      const int t = iy * nx + ix;
+      if (bad && bad[t]) continue;
+      const int qx = X - min(ix * Sx, Wo - Tx);
+      const size_t p = (size_t)t * C + c;
+      const float* src = tiles + p * Ty * Tx;
+      float sd = 1.f, m = 0.f;
+      if (off) {
+        sd = dv[p];
+        m = off[p];
+      }
+      int w[kV];
+#pragma unroll
+      for (int e = 0; e < kV; ++e) {
+        w[e] = wy * overlap_weight(qx + e, Tx, Rx);
+        wsum[e] += w[e];
+      }
+      ++cnt;
+      int rem = variants;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < K) {
+          const int f = __ffs(rem) - 1;
+          rem &= rem - 1;
+          float v[kV];
+          ensemble_read<kV>(src + (size_t)j * slab, f, Ty, Tx, qy, qx, v);
+          if (off) {
+#pragma unroll
+            for (int e = 0; e < kV; ++e) v[e] = blend_denorm(v[e], sd, m);
+          }
+#pragma unroll
+          for (int e = 0; e < kV; ++e) {
+            acc[j][e] = fmaf((float)w[e], v[e], acc[j][e]);
+            one[j][e] = v[e];
+          }
+        }
+      }
+    }
+  }
+  float mu[kV], sp[kV];
+  const float fk = (float)K;
+#pragma unroll
+  for (int e = 0; e < kV; ++e) {
+    float B[8], D[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) B[j] = j >= K ? 0.f : cnt == 1 ? one[j][e] : acc[j][e] / (float)wsum[e];
+    mu[e] = ensemble_sum(B, K) / fk;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = __fsub_rn(B[j], mu[e]);
+      D[j] = __fmul_rn(d, d);
+    }
+    sp[e] = sqrtf(ensemble_sum(D, K) / fk);
+    if (cnt == 0) mu[e] = sp[e] = nan;  // no cover left: the canonical NaN, as tiles_blend_kernel
+  }
+  if constexpr (kV == 4) {
+    *reinterpret_cast<float4*>(mean + o) = make_float4(mu[0], mu[1], mu[2], mu[3]);
+    if (spread) *reinterpret_cast<float4*>(spread + o) = make_float4(sp[0], sp[1], sp[2], sp[3]);
+  } else {
+    mean[o] = mu[0];
+    if (spread) spread[o] = sp[0];
+  }
+}
+
+int tiles_blend_ensemble_launch(const float* tiles, int variants, const float* off, const float* dv, const int* bad,
+                                int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src,
+                                int scale, float* mean, float* spread, hipStream_t st) {
+  if (variants < 1 || variants > 255) return SRMI_ERR_ARG;
+  if (mask_src && (scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale)) return SRMI_ERR_ARG;
+  // from here as tiles_blend_any_launch
+  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.z
+  const int ny = overlap_count(Ho, Ty, Sy), nx = overlap_count(Wo, Tx, Sx);
+  if (ny < 0 || nx < 0) return SRMI_ERR_ARG;
+  const long long wy = (long long)(Ty / Sy + 2) * (Ty - Sy + 1), wx = (long long)(Tx / Sx + 2) * (Tx - Sx + 1);
+  if (Ho > 65535 || (long long)ny * nx > 0x7fffffffLL || wy * wx > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if ((variants & 0xf0) && Ty != Tx) return SRMI_ERR_SHAPE;  // a swap of a rectangular tile
+  if (!tiles || !mean || (off && !dv)) return SRMI_ERR_ARG;
+  const int K = __builtin_popcount((unsigned)variants);
+  const bool vec = Tx % 4 == 0 && Sx % 4 == 0 && Wo % 4 == 0 && ((uintptr_t)tiles & 15) == 0 &&
+                   ((uintptr_t)mean & 15) == 0 && ((uintptr_t)spread & 15) == 0 && (!mask_src || scale % 4 == 0);
+#define SRMI_BLEND_ENS(V, MASK)                                                                                    \
+  hipLaunchKernelGGL((tiles_blend_ensemble_kernel<V, MASK>), dim3((Wo / V + 15) / 16, (Ho + 15) / 16, C), dim3(256), \
+                     0, st, tiles, variants, K, off, dv, bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, mask_src, scale,    \
+                     mean, spread)
+  if (mask_src) {
+    if (vec) SRMI_BLEND_ENS(4, true);
+    else SRMI_BLEND_ENS(1, true);
+  } else {
+    if (vec) SRMI_BLEND_ENS(4, false);
+    else SRMI_BLEND_ENS(1, false);
+  }
+#undef SRMI_BLEND_ENS
+  SRMI_CHECK_LAUNCH();
+  return 0;
 }
 
 // ------------------------------------------------------ dataset tile statistics

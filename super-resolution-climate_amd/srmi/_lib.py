@@ -124,6 +124,9 @@ _SIGS = {
                                              P, P, P, P, P, P, C.c_int, P, P], C.c_int),
     "srmi_tiles_blend_masked": ([P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int,
                                  P, P], C.c_int),
+    "srmi_tiles_dihedral": ([P, C.c_longlong, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
+    "srmi_tiles_blend_ensemble": ([P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P,
+                                   C.c_int, P, P, P], C.c_int),
     "srmi_rmse_partial_masked": ([P, P, P, C.c_size_t, P, P], C.c_int),
     "srmi_tiles_dry": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P], C.c_int),
     "srmi_tiles_fill": ([P, C.c_longlong, C.c_int, C.c_int, P, P], C.c_int),

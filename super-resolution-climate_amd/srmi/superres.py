@@ -57,10 +57,25 @@ NaN and counts only the pixels where both sides are finite
 (``srmi_rmse_partial_masked``).  No host synchronisation anywhere: the fill's trip count
 is decided on the device, so ``graph=True`` works and one captured graph serves regions
 with different coasts.
+
+Self-ensemble (``ensemble=4`` or ``8``)
+---------------------------------------
+The "+" variant of the RCAN / EDSR papers, and a per-pixel spread.  No retraining: the
+model runs on K dihedral variants of every tile (``srmi_tiles_dihedral``; variant f is
+the reference's xyflip -- bit 0 flips x, bit 1 flips y, bit 2 then swaps the axes; 4
+takes the flips, 8 the swaps as well, which need a square tile), and the blend
+(``srmi_tiles_blend_ensemble``) reads every output back through the inverse map, blends
+each variant exactly as above and returns their mean as 'model' and their standard
+deviation (ddof 0) as 'spread'.  The network is not dihedral-equivariant (zero padding,
+PixelShuffle and the learned filters break the symmetry), so the mean is a real gain and
+the spread the cheapest honest proxy for where to trust the field.  With ``land=True`` the
+variants are transforms of the FILLED tile, and both images are re-masked.  The cost is
+K forwards; the two added launches are noise beside them.
 """
 from __future__ import annotations
 
 import math
+import numbers
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -104,12 +119,42 @@ def lib_overlap_count(L: int, t: int, S: int) -> int:
     return n
 
 
+def ensemble_variants(ensemble, tile_lr: Tuple[int, int]) -> Tuple[int, ...]:
+    """The dihedral variants of a self-ensemble, ascending: 1 -> (0,), 4 -> the flips
+    (0, 1, 2, 3), 8 -> all of (0, .., 7); or a sequence of variant indices -- non-empty,
+    unique, within 0 .. 7 and holding 0 (the untransformed tile) -- returned sorted.
+    Variant f is xyflip's: bit 0 flips x, bit 1 flips y, bit 2 swaps the axes, so f >= 4
+    needs a square tile.  Anything else: ValueError."""
+    ty, tx = (int(v) for v in tile_lr)
+    if isinstance(ensemble, bool):
+        raise ValueError(f"ensemble {ensemble!r}: 1, 4, 8 or a sequence of variant indices")
+    if isinstance(ensemble, numbers.Integral):
+        if ensemble not in (1, 4, 8):
+            raise ValueError(f"ensemble {ensemble!r}: 1, 4, 8 or a sequence of variant indices")
+        var = tuple(range(int(ensemble)))
+    else:
+        try:
+            items = list(ensemble)
+        except TypeError:
+            raise ValueError(f"ensemble {ensemble!r}: 1, 4, 8 or a sequence of variant indices") from None
+        if not items or any(isinstance(f, bool) or not isinstance(f, numbers.Integral) for f in items):
+            raise ValueError(f"ensemble {ensemble!r}: a non-empty sequence of integer variant indices")
+        items = [int(f) for f in items]
+        if len(set(items)) != len(items) or min(items) < 0 or max(items) > 7 or 0 not in items:
+            raise ValueError(f"ensemble {ensemble!r}: unique variant indices within 0 .. 7, variant 0 among them")
+        var = tuple(sorted(items))
+    if var[-1] >= 4 and ty != tx:
+        raise ValueError(f"ensemble {ensemble!r}: the variants that swap the axes (>= 4) need a square tile, tile_lr "
+                         f"is {(ty, tx)}; use ensemble=4 (the flips only)")
+    return var
+
+
 # ---------------------------------------------------------------- the class
 class RegionSuperResolver:
     def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw_lr: Tuple[int, int, int],
                  tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
                  task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
-                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25):
+                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25, ensemble=1):
         """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
         runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
         overlap).
@@ -143,7 +188,15 @@ class RegionSuperResolver:
         land: the region may hold NaN (land); see the module docstring.  min_wet, in
         (0, 1]: the share of a tile plane that must be wet in every channel for the tile
         to be used (the ABI gets max(1, ceil(min_wet ty tx)) pixels).  land=False is the
-        object as it was, bit for bit."""
+        object as it was, bit for bit.
+
+        ensemble: 1, 4, 8 or a sequence of variant indices (``ensemble_variants``); see
+        the module docstring.  With K > 1 variants the K n transformed tiles go through
+        the same engines (micro and max_batch split K n tiles), 'model' is the mean of
+        the K blended outputs and the images gain 'spread'.  The tile and output buffers
+        and the forward's time grow K-fold, and the 4 GiB bound above is reached by a
+        chunk of K n tiles as by any other: keep max_batch.  ensemble=1 is the object as
+        it was, bit for bit."""
         if task is None:  # the active srmi ConfigContext's task section, if any
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
@@ -168,6 +221,9 @@ class RegionSuperResolver:
             raise ValueError(f"region {(h, w)} smaller than one tile {(ty, tx)}")
         if not (0 <= ry <= ty // 2 and 0 <= rx <= tx // 2):
             raise ValueError(f"overlap {(ry, rx)} outside 0 .. tile // 2 = {(ty // 2, tx // 2)}")
+        self.variants = ensemble_variants(ensemble, (ty, tx))
+        self.vmask = sum(1 << f for f in self.variants)
+        K = self.K = len(self.variants)
         s = spec.scale
         self.C, self.h, self.w, self.ty, self.tx, self.s = C, h, w, ty, tx, s
         self.land = bool(land)
@@ -193,13 +249,22 @@ class RegionSuperResolver:
             self.off.copy_(off)
             self.div.copy_(div)
         self.bad = torch.zeros(n, dtype=torch.int32, device=d)
-        self.sr = torch.empty((n, C, ty * s, tx * s), **f32)
+        if K == 1:
+            self.sr = torch.empty((n, C, ty * s, tx * s), **f32)
+            self._fin, self._fout = self.tiles, self.sr  # what the forward reads and writes
+        else:
+            self.vtiles = torch.empty((K, n, C, ty, tx), **f32)  # the variants of self.tiles
+            self.sr = torch.empty((K, n, C, ty * s, tx * s), **f32)  # their outputs, in the transformed frame
+            self._fin, self._fout = self.vtiles.view(K * n, C, ty, tx), self.sr.view(K * n, C, ty * s, tx * s)
         self.images = {"input": self.region, "interpolated": torch.empty((C, h * s, w * s), **f32),
                        "model": torch.empty((C, h * s, w * s), **f32)}
+        if K > 1:
+            self.images["spread"] = torch.empty((C, h * s, w * s), **f32)
         if self.land:
             self.nwet = torch.zeros((n, C), dtype=torch.int32, device=d)
             self.up = torch.empty((n, C, ty * s, tx * s), **f32)  # the tiled baseline's tiles
             self.images["nwet"] = self.nwet
+        n = self.nfwd = K * n  # the forward's tiles: the split and the chunks are taken over all of them
         if micro is None:
             micro = 2 if n >= 32 else 1
         self.micro = max(1, min(int(micro), n))
@@ -240,14 +305,14 @@ class RegionSuperResolver:
             sk.wait_event(self.ev_fork)
         a = 0
         for k, e in enumerate(self.engs):
-            b = min(self.n, a + self.split[k])
+            b = min(self.nfwd, a + self.split[k])
             for c0 in range(a, b, e.batch):
                 c1 = min(b, c0 + e.batch)
                 if self.streams[k] is None:
-                    e.forward(self.params, self.tiles[c0:c1], out=self.sr[c0:c1])
+                    e.forward(self.params, self._fin[c0:c1], out=self._fout[c0:c1])
                 else:
                     with torch.cuda.stream(self.streams[k]):
-                        e.forward(self.params, self.tiles[c0:c1], out=self.sr[c0:c1])
+                        e.forward(self.params, self._fin[c0:c1], out=self._fout[c0:c1])
             a = b
         for sk, ev in zip(self.streams[1:], self.ev_join):
             ev.record(sk)
@@ -259,8 +324,19 @@ class RegionSuperResolver:
              self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.region), s, ptr(out),
              stream_handle())
 
+    def _expand(self):
+        """self.tiles -> self.vtiles: the K dihedral variants of every tile plane."""
+        call("srmi_tiles_dihedral", ptr(self.tiles), self.n * self.C, self.ty, self.tx, self.vmask, ptr(self.vtiles),
+             stream_handle())
+
     def _blend(self):
         s = self.s
+        if self.K > 1:
+            call("srmi_tiles_blend_ensemble", ptr(self.sr), self.vmask, ptr(self.off), ptr(self.div), ptr(self.bad),
+                 self.C, self.ty * s, self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s,
+                 ptr(self.region) if self.land else None, s, ptr(self.images["model"]), ptr(self.images["spread"]),
+                 stream_handle())
+            return
         if self.land:
             self._blend_masked(self.sr, self.images["model"])
             return
@@ -269,6 +345,8 @@ class RegionSuperResolver:
 
     def _run(self):
         self._cut()
+        if self.K > 1:
+            self._expand()
         self._forward()
         if self.land:  # the tiled baseline: every tile plane upsampled alone, blended like the model's
             upsample(self.tiles, self.s, out=self.up, mode=self.umode)
@@ -298,7 +376,11 @@ class RegionSuperResolver:
 
         land=True: lr_region may hold NaN; 'model' and 'interpolated' (then the tiled
         baseline) are NaN exactly on the upsampled dry pixels and where every covering
-        tile is bad, and 'nwet' [n, C] int32 holds the wet count of every tile plane."""
+        tile is bad, and 'nwet' [n, C] int32 holds the wet count of every tile plane.
+
+        ensemble > 1: 'model' is the mean of the K back-transformed, blended outputs and
+        'spread' [C, s h, s w] their standard deviation (ddof 0), in the physical units
+        of 'model' and NaN where 'model' is; 'interpolated' is what it is without."""
         if tuple(lr_region.shape) != (self.C, self.h, self.w):
             raise ValueError(f"region shape {tuple(lr_region.shape)} != {(self.C, self.h, self.w)}")
         self.region.copy_(lr_region)

@@ -34,6 +34,17 @@ window of its own.  Reports the median and the spread of each, the stage's share
 baseline there is -- the time of the numpy oracle (tests/spectra_oracle.py, fp64) on the
 host for the same two pairs of fields, run once, with the device's largest deviation from
 it; writes profiles/spectra_bench.json.
+
+--ensemble K [K ...]: what does the self-ensemble cost, and what does it give?  One
+RegionSuperResolver(ensemble=K) per K in {1, 4, 8} (1 always among them) on the default
+region at the last of --overlaps, the arms alternating window by window.  Reports the HR
+MPix/s of each, t(K) / (K t(1)) per pair of neighbouring windows (median and spread; the
+forward dominates, so it should sit near 1), the eager time of the two launches the
+ensemble adds (srmi_tiles_dihedral, srmi_tiles_blend_ensemble) and their share of the
+largest K's region, and -- on a synthetic truth through ``score`` -- the RMSE of 'model' at
+each K and the correlation of 'spread' with |model - truth|; writes
+profiles/ensemble_bench.json.  The weights are default_init_'s, untrained: the last two
+describe the tool's network, not a trained one's gain.
 """
 import argparse
 import json
@@ -207,6 +218,73 @@ def spectra_main(a, spec, params, dev, kw):
     return res
 
 
+def ensemble_main(a, spec, params, lr, dev, kw):
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.superres import RegionSuperResolver
+    r, s = a.overlaps[-1], spec.scale
+    Ks = sorted(set([1] + list(a.ensemble)))
+    rs = {K: RegionSuperResolver(spec, params, tuple(lr.shape), (a.tile, a.tile), (r, r), device=dev,
+                                 graph=not a.no_graph, ensemble=K, **kw) for K in Ks}
+    for K in Ks:
+        for _ in range(a.warmup):
+            out = rs[K].super_resolve(lr)
+        torch.cuda.synchronize()
+        if not bool(torch.isfinite(out["model"]).all()):
+            raise SystemExit(f"superres_bench: ensemble {K}: non-finite output")
+    st = torch.cuda.current_stream()
+    ms = {K: [] for K in Ks}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for K in Ks:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(a.regions):
+                rs[K].super_resolve(lr)
+            e1.record(st)
+            e1.synchronize()
+            ms[K].append(e0.elapsed_time(e1) / a.regions)
+    mpix = (a.side * s) ** 2 / 1e6
+    res = {"tool": "superres_bench --ensemble", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 super_resolve, 1 var, {a.side}^2 LR region -> {a.side * s}^2 HR, LR "
+                                  f"tile {a.tile}, overlap {r}", "graph": not a.no_graph, "warmup": a.warmup,
+                      "repeats": a.repeats, "regions_per_window": a.regions,
+                      "weights": "default_init_ (untrained): the RMSE and the correlation say how the ensemble of "
+                                 "THIS network behaves, not what a trained one gains"},
+           "hr_mpix_per_region": round(mpix, 3), "ensemble": {}}
+    for K in Ks:
+        med = statistics.median(ms[K])
+        ratios = [x / (K * y) for x, y in zip(ms[K], ms[1])]  # per pair of neighbouring windows
+        res["ensemble"][str(K)] = {
+            "variants": list(rs[K].variants), "forward_tiles": rs[K].nfwd, "engines": rs[K].micro,
+            "chunk_tiles": [e.batch for e in rs[K].engs], "ms_per_region": round(med, 3),
+            "ms_min_max": [round(min(ms[K]), 3), round(max(ms[K]), 3)], "hr_mpix_per_s": round(mpix / (med * 1e-3), 2),
+            "t_over_K_t1": {"median": round(statistics.median(ratios), 4),
+                            "min_max": [round(min(ratios), 4), round(max(ratios), 4)]}}
+    # the two launches the ensemble adds (the blend replaces the plain one), eager, in the largest K's run
+    Kmax = Ks[-1]
+    if Kmax > 1:
+        big = rs[Kmax]
+        expand, blend, plain = timed(big._expand), timed(big._blend), timed(rs[1]._blend)
+        total = statistics.median(ms[Kmax])
+        hr_px = (a.side * s) ** 2
+        res["new_launches"] = {
+            "K": Kmax, "dihedral_ms": round(expand, 4), "blend_ensemble_ms": round(blend, 4),
+            "plain_blend_ms": round(plain, 4), "share_of_region": round((expand + blend) / total, 5),
+            "blend_ensemble_gb_per_s": round(4.0 * (Kmax + 2) * hr_px / (blend * 1e-3) / 1e9, 1),
+            "dihedral_gb_per_s": round(4.0 * (Kmax + 1) * big.tiles.numel() / (expand * 1e-3) / 1e9, 1)}
+    # a synthetic truth through score: the RMSE of 'model' at each K, and how |model - truth| follows 'spread'
+    hr = torch.tensor(synthetic_hr(1, 1, a.side * s, 98)[0]).to(dev)
+    res["truth"] = {}
+    for K in Ks:
+        images, losses = rs[K].score(hr)
+        entry = {"rmse_model": float(losses["model"]), "rmse_interpolated": float(losses["interpolated"])}
+        if K > 1:
+            err, sp = (images["model"] - hr).abs().double().flatten(), images["spread"].double().flatten()
+            entry["corr_spread_abs_error"] = round(float(torch.corrcoef(torch.stack([sp, err]))[0, 1]), 4)
+            entry["spread_median"] = float(sp.median())
+        res["truth"][str(K)] = entry
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=1024, help="LR region side")
@@ -221,16 +299,19 @@ def main():
                     help="paint a coast with about this share of dry pixels and compare land=True with land=False")
     ap.add_argument("--spectra", type=int, nargs="?", const=256, default=None, metavar="WINDOW",
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
+    ap.add_argument("--ensemble", type=int, nargs="+", default=None, metavar="K", choices=(1, 4, 8),
+                    help="time RegionSuperResolver(ensemble=K) for each K (1 is always among them)")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
-                                                "spectra_bench.json)")
+                                                "spectra_bench.json, ensemble_bench.json)")
     a = ap.parse_args()
-    if a.land is not None and a.spectra is not None:
-        raise SystemExit("superres_bench: --land and --spectra are separate runs")
+    if sum(x is not None for x in (a.land, a.spectra, a.ensemble)) > 1:
+        raise SystemExit("superres_bench: --land, --spectra and --ensemble are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
-                             "spectra_bench.json" if a.spectra is not None else "superres_bench.json")
+                             "spectra_bench.json" if a.spectra is not None else
+                             "ensemble_bench.json" if a.ensemble is not None else "superres_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("superres_bench: no GPU (there is no CPU path to time)")
     from oracle.rcan_oracle import synthetic_hr
@@ -246,9 +327,10 @@ def main():
     default_init_(params, table, 0)
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
-    if a.land is not None or a.spectra is not None:
+    if a.land is not None or a.spectra is not None or a.ensemble is not None:
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
-                          spectra_main(a, spec, params, dev, kw))
+                          spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
+                          ensemble_main(a, spec, params, lr, dev, kw))
         print(line)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
