@@ -66,6 +66,12 @@
  *   srmi_spectral_loss_dy        -> a Fourier-amplitude term beside the pixel loss of a
  *                                   training step.  No reference counterpart: the
  *                                   reference trains on a pixel loss alone.
+ *   srmi_consistency_residual,
+ *   srmi_consistency_iterate,
+ *   srmi_consistency_apply       -> back-projection of a super-resolved field onto its
+ *                                   coarse input, iterated in LR space.  No reference
+ *                                   counterpart: the reference never starts from a coarse
+ *                                   field.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -608,6 +614,49 @@ int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int ki
 int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
 int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
                  size_t workspace_bytes, float* out, int* nused, void* stream);
+
+/* ---- consistency with the coarse input (no reference counterpart) -------- */
+/* Iterative back-projection x <- x + U(lr - D x) of an HR field x [C][h s][w s] onto the LR
+ * field lr [C][h][w] it was made from, D = F.interpolate at 1 / s in `dmode`, U =
+ * F.interpolate at s in `umode` (SRMI_INTERP_*, align_corners=False).  At an even s, D
+ * reads only the s x s children of an LR pixel (bicubic: taps s/2 - 2 .. s/2 + 1 per axis
+ * with [-3, 19, 19, -3] / 32, which needs s >= 4; bilinear: s/2 - 1 and s/2 with 1/2 each),
+ * so with r0 = lr - D x0 and E = I - D U the K-th iterate is x_K = x0 + U(R_K), R_K = sum_{k
+ * < K} E^k r0, and its residual lr - D x_K = E^K r0: the loop runs on LR-size buffers.
+ * Along one axis D U is the stencil g[-2 .. 2] (g[-2] = g[2] = 0 when U is bilinear) read
+ * at indices clamped to the field -- U's own edge rule; in 2-D it is g (x) g.
+ * Mask rule: an LR cell is ACTIVE iff lr is finite there and every tap of D in x0 is
+ * finite; r is 0 at the other cells at every step (the operator is M E M), and the apply
+ * step adds U(R) to every finite HR pixel and never writes a non-finite one.
+ * All three: fp32, on `stream`, no host synchronisation, no atomics, no allocation --
+ * capturable and bit-identical from run to run.  A missing buffer or a mode that is not
+ * SRMI_INTERP_BILINEAR / _BICUBIC: SRMI_ERR_ARG; C, h, w < 1, a scale that is odd, above
+ * 64 or below 4 (2 where only bilinear taps are read), or (h s)(w s) >= 2^31:
+ * SRMI_ERR_SHAPE; nothing is enqueued in either case. */
+/* r0 [C][h][w] = lr - D(hr) at the active cells, 0 elsewhere; active [C][h][w] int32 = 1 /
+ * 0.  Every element of both is written.  Per cell the tap rows of its block are read once
+ * (16-byte loads along rows where scale is 4 or 8 and hr is 16-byte aligned) and summed as
+ * srmi_downsample does: per row the taps in ascending x, then the rows in ascending y. */
+int srmi_consistency_residual(const float* hr, const float* lr, int C, int h, int w, int scale, int dmode, float* r0,
+                              int* active, void* stream);
+/* One step on LR-size buffers: R = (first ? 0 : R) + r, then r_out = r - (D U) r at the
+ * active cells and 0 elsewhere -- the (2 radius + 1)^2-tap clamped-index stencil, radius 2
+ * (U bicubic) or 1 (U bilinear), x taps summed per row, rows then summed; g is derived on
+ * the host in double from ATen's cubic (A = -0.75) / linear weights of (scale, umode,
+ * dmode) and rounded to fp32.  Started from r = r0 with first = 1 and ping-ponged, K
+ * launches leave R = R_K and r_out = E^K r0, the residual of the corrected field.  Every
+ * element of R and r_out is written.  r, R and r_out must be three different buffers:
+ * SRMI_ERR_ARG otherwise. */
+int srmi_consistency_iterate(const float* r, const int* active, int C, int h, int w, int scale, int umode, int dmode,
+                             int first, float* R, float* r_out, void* stream);
+/* hr [C][h s][w s] += U(R) at every finite pixel of hr, with srmi_upsample's (bicubic) /
+ * srmi_interpolate's (bilinear) coordinate and weight arithmetic evaluated in the kernel;
+ * U(R) is never materialised.  A thread owns the `scale` pixels of one row that share an
+ * LR parent and reads their 4 x 5 (2 x 3) neighbourhood of R once, combined along y first.
+ * A non-finite pixel of hr is never stored to: its bits (NaN payloads included) stay.  R
+ * must be finite (srmi_consistency_iterate's is).  16-byte accesses where scale % 4 == 0
+ * and hr is 16-byte aligned. */
+int srmi_consistency_apply(const float* R, int C, int h, int w, int scale, int umode, float* hr, void* stream);
 
 /* ---- the spectral loss term (no reference counterpart) ------------------ */
 /* A Fourier-space term beside the pixel loss of a training step: the windowed amplitudes

@@ -38,6 +38,7 @@ FWD_TRACE_SLOTS = {"LO": 0, "PPOOL": 1, "RF": 2, "HB": 3, "T": 4, "REC": 5}
 TILE_LOSS_SUB = 16  # parts per tile of srmi_tile_loss_parts
 
 SRMI_ERR_ARG = -10001
+SRMI_ERR_SHAPE = -10002
 ERRORS = {-10001: "SRMI_ERR_ARG", -10002: "SRMI_ERR_SHAPE", -10003: "SRMI_ERR_WORKSPACE",
           -10004: "SRMI_ERR_UNSUPPORTED"}
 
@@ -156,6 +157,10 @@ _SIGS = {
     "srmi_spectral_loss_dy": ([P, C.c_size_t, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P, P, P],
                               C.c_int),
     "srmi_tiles_gather_dev": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P], C.c_int),
+    "srmi_consistency_residual": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P], C.c_int),
+    "srmi_consistency_iterate": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P],
+                                 C.c_int),
+    "srmi_consistency_apply": ([P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

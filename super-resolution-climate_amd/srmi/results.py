@@ -193,12 +193,21 @@ def save_superres_results(path_for_var, images: Dict[str, object], varnames: Seq
     supplied some.  path_for_var: varname -> file path (e.g. a results_path partial).
     'spread' [C, s h, s w] (RegionSuperResolver(ensemble > 1)) is written as a fourth
     variable when ``images`` holds it; the file is unchanged otherwise.
+    'residual' [C, h, w] (RegionSuperResolver(consistent > 0): the input minus the
+    downsample of the uncorrected model) is written on the input's ys / xs when ``images``
+    holds it; the file is unchanged otherwise.
     No reference counterpart (its files come from process_image only)."""
     missing = [k for k in ("input", "interpolated", "model") if k not in images]
     if missing:
         raise ValueError(f"super_resolve images lack {missing}")
     keys = ("input", "interpolated", "model") + (("spread",) if "spread" in images else ())
     per_var = image_results({k: images[k] for k in keys}, varnames)
+    if "residual" in images:
+        ren = {"y": "ys", "x": "xs"}
+        for v, d in image_results({"residual": images["residual"]}, varnames).items():
+            r = d["residual"]
+            per_var[v]["residual"] = Var(tuple(ren[k] for k in r.dims), r.values,
+                                         {ren[k]: c for k, c in r.coords.items()})
     return [save_inference_results(path_for_var(v), per_var[v], dict(losses or {})) for v in varnames]
 
 
@@ -210,7 +219,7 @@ def load_inference_results(path: str) -> Tuple[Dict[str, Var], Dict[str, float]]
         keys = f.loss_keys.decode() if isinstance(f.loss_keys, bytes) else str(f.loss_keys)
         vals = np.atleast_1d(f.loss_values).tolist()
         losses = dict(zip(keys.split(",") if keys else [], vals))
-        names = [n for n in ("input", "target", "interpolated", "model", "spread") if n in f.variables]
+        names = [n for n in ("input", "target", "interpolated", "model", "spread", "residual") if n in f.variables]
         out: Dict[str, Var] = {}
         for n in names:
             v = f.variables[n]

@@ -71,6 +71,26 @@ PixelShuffle and the learned filters break the symmetry), so the mean is a real 
 the spread the cheapest honest proxy for where to trust the field.  With ``land=True`` the
 variants are transforms of the FILLED tile, and both images are re-masked.  The cost is
 K forwards; the two added launches are noise beside them.
+
+Consistency (``consistent=K``, 1 <= K <= 16)
+--------------------------------------------
+Nothing above ties D('model') to the input, D being the task's downsample: the tiles are
+normalised with LR statistics, the seams are blended and the network is unconstrained.
+``consistent=K`` runs K steps of iterative back-projection, x <- x + U(input - D x) with U
+the task's upsample, on the blended 'model' (after the ensemble mean), in physical units and
+in place.  At an even scale D reads only the s x s children of an LR pixel, so the loop
+never runs at HR size: with r0 = input - D x0 and E = I - D U it is x_K = x0 + U(R_K), R_K =
+sum_{k < K} E^k r0, and D U is a 5-tap (3-tap for a bilinear U) clamped-index stencil per
+axis in LR space.  One read of the HR field (``srmi_consistency_residual``), K stencils on
+LR-size buffers (``srmi_consistency_iterate``) and one read-modify-write of the HR field
+(``srmi_consistency_apply``).  E contracts for all four mode pairs at s = 4 and 8 (spectral
+radius 0.03 for cubic / cubic at s = 4, 0.43 for linear / linear).
+The images gain 'residual' = r0 [C, h, w], the raw model's inconsistency, and
+'residual_left' = E^K r0, what the corrected field still misses.  An LR cell takes part iff
+its input is finite and every tap of D in 'model' is; the others have a zero residual at
+every step, and a non-finite pixel of 'model' is never written, so with ``land=True`` and
+bad tiles the NaN set and bits of 'model' are what they were.  'interpolated' and 'spread'
+are untouched; ``score`` and ``score_spectra`` score the corrected field.
 """
 from __future__ import annotations
 
@@ -80,7 +100,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ._lib import SRMI_ERR_ARG, SRMI_NORM_AFFINE, call, load, ptr, stream_handle
+from ._lib import (SRMI_ERR_ARG, SRMI_INTERP_BICUBIC, SRMI_INTERP_BILINEAR, SRMI_NORM_AFFINE, call, load, ptr,
+                   stream_handle)
 from .engine import Engine, NetSpec, downsample, engine_stream, upsample
 
 SUPPORTED_NORMS = ("lnorm", "lscale", "gnorm", "gscale")
@@ -149,12 +170,37 @@ def ensemble_variants(ensemble, tile_lr: Tuple[int, int]) -> Tuple[int, ...]:
     return var
 
 
+INTERP_MODES = {"bilinear": SRMI_INTERP_BILINEAR, "bicubic": SRMI_INTERP_BICUBIC}
+MAX_CONSISTENT = 16
+
+
+def check_consistent(consistent, scale: int, dmode: str, umode: str) -> int:
+    """The ``consistent`` argument of RegionSuperResolver as an int: an integer 0 .. 16, and,
+    when positive, an even scale (>= 4 under a bicubic downsample, whose taps would leave
+    the s x s block otherwise) and bilinear / bicubic modes.  Anything else: ValueError."""
+    if isinstance(consistent, bool) or not isinstance(consistent, numbers.Integral):
+        raise ValueError(f"consistent {consistent!r}: an integer 0 .. {MAX_CONSISTENT}")
+    k = int(consistent)
+    if not 0 <= k <= MAX_CONSISTENT:
+        raise ValueError(f"consistent {consistent!r} outside 0 .. {MAX_CONSISTENT}")
+    if k == 0:
+        return 0
+    if dmode not in INTERP_MODES or umode not in INTERP_MODES:
+        raise ValueError(f"consistent={k} needs bilinear / bicubic resampling, the task has {dmode!r} / {umode!r}")
+    smin = 4 if dmode == "bicubic" else 2
+    if int(scale) % 2 or int(scale) < smin:
+        raise ValueError(f"consistent={k} needs an even scale >= {smin} under a {dmode} downsample, the model's is "
+                         f"{scale}")
+    return k
+
+
 # ---------------------------------------------------------------- the class
 class RegionSuperResolver:
     def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw_lr: Tuple[int, int, int],
                  tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
                  task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
-                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25, ensemble=1):
+                 device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25, ensemble=1,
+                 consistent: int = 0):
         """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
         runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
         overlap).
@@ -196,7 +242,12 @@ class RegionSuperResolver:
         the K blended outputs and the images gain 'spread'.  The tile and output buffers
         and the forward's time grow K-fold, and the 4 GiB bound above is reached by a
         chunk of K n tiles as by any other: keep max_batch.  ensemble=1 is the object as
-        it was, bit for bit."""
+        it was, bit for bit.
+
+        consistent: an integer 0 .. 16, the steps of back-projection applied to 'model'
+        (see the module docstring).  It needs an even scale, >= 4 when the task's
+        downsample is bicubic: ValueError otherwise.  consistent=0 is the object as it
+        was, bit for bit."""
         if task is None:  # the active srmi ConfigContext's task section, if any
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
@@ -210,6 +261,7 @@ class RegionSuperResolver:
         if self.norm_mode == SRMI_NORM_AFFINE and stats is None:
             raise ValueError(f"norm {self.norm!r} needs the dataset statistics (stats=NormStats)")
         self.dmode, self.umode = interp_mode(task, True), interp_mode(task, False)
+        self.consistent = check_consistent(consistent, spec.scale, self.dmode, self.umode)
         self.spec = spec
         self.device = device or params.device
         C, h, w = (int(v) for v in region_chw_lr)
@@ -264,6 +316,13 @@ class RegionSuperResolver:
             self.nwet = torch.zeros((n, C), dtype=torch.int32, device=d)
             self.up = torch.empty((n, C, ty * s, tx * s), **f32)  # the tiled baseline's tiles
             self.images["nwet"] = self.nwet
+        if self.consistent:
+            # r0, the ping-pong pair of the iteration, its sum R and the active mask: LR size
+            self._cr = [torch.empty((C, h, w), **f32) for _ in range(3 if self.consistent > 1 else 2)]
+            self._cR = torch.empty((C, h, w), **f32)
+            self._cact = torch.empty((C, h, w), dtype=torch.int32, device=d)
+            self.images["residual"] = self._cr[0]
+            self.images["residual_left"] = self._cr[1 + (self.consistent - 1) % 2]
         n = self.nfwd = K * n  # the forward's tiles: the split and the chunks are taken over all of them
         if micro is None:
             micro = 2 if n >= 32 else 1
@@ -354,6 +413,23 @@ class RegionSuperResolver:
         else:
             upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
         self._blend()
+        if self.consistent:
+            self._correct()
+
+    def _correct(self):
+        """'model' <- 'model' + U(R_K) at its finite pixels; 'residual', 'residual_left'."""
+        C, h, w, s, st = self.C, self.h, self.w, self.s, stream_handle()
+        um, dm = INTERP_MODES[self.umode], INTERP_MODES[self.dmode]
+        model = self.images["model"]
+        call("srmi_consistency_residual", ptr(model), ptr(self.region), C, h, w, s, dm, ptr(self._cr[0]),
+             ptr(self._cact), st)
+        src = self._cr[0]
+        for k in range(self.consistent):
+            dst = self._cr[1 + k % 2]
+            call("srmi_consistency_iterate", ptr(src), ptr(self._cact), C, h, w, s, um, dm, int(k == 0), ptr(self._cR),
+                 ptr(dst), st)
+            src = dst
+        call("srmi_consistency_apply", ptr(self._cR), C, h, w, s, um, ptr(model), st)
 
     def _capture(self):
         self._run()  # warm-up outside capture (uploads engine tables)
@@ -380,7 +456,12 @@ class RegionSuperResolver:
 
         ensemble > 1: 'model' is the mean of the K back-transformed, blended outputs and
         'spread' [C, s h, s w] their standard deviation (ddof 0), in the physical units
-        of 'model' and NaN where 'model' is; 'interpolated' is what it is without."""
+        of 'model' and NaN where 'model' is; 'interpolated' is what it is without.
+
+        consistent > 0: 'model' is the corrected field (the module docstring), 'residual'
+        [C, h, w] the input minus the downsample of the uncorrected one and
+        'residual_left' [C, h, w] what the corrected one still misses, both 0 at the LR
+        cells that take no part; 'interpolated' and 'spread' are what they are without."""
         if tuple(lr_region.shape) != (self.C, self.h, self.w):
             raise ValueError(f"region shape {tuple(lr_region.shape)} != {(self.C, self.h, self.w)}")
         self.region.copy_(lr_region)

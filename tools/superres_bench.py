@@ -45,6 +45,18 @@ largest K's region, and -- on a synthetic truth through ``score`` -- the RMSE of
 each K and the correlation of 'spread' with |model - truth|; writes
 profiles/ensemble_bench.json.  The weights are default_init_'s, untrained: the last two
 describe the tool's network, not a trained one's gain.
+
+--consistent K [K ...]: what does the consistency correction cost, and what does it leave?
+One RegionSuperResolver(consistent=K) per K (0 always among them) on the default region at
+the last of --overlaps, the arms alternating window by window on one device.  Reports the
+HR MPix/s of each and t(K) / t(0) per pair of neighbouring windows, the eager time of the
+launches the largest K adds (residual, K iterations, apply) with the bytes/s they achieve
+against 3 C (s h) (s w) 4 bytes (one read of the HR field, one read-modify-write), the rms
+of 'residual' and of 'residual_left', the rms of D('model') - input through the existing
+downsample, and ``score``'s RMSE against a synthetic truth for every arm; writes
+profiles/consistency_bench.json.  No pass / fail bar: none of it had been measured before,
+and the weights are default_init_'s, untrained -- the residuals and RMSEs describe the
+tool's network, not a trained one.
 """
 import argparse
 import json
@@ -285,6 +297,73 @@ def ensemble_main(a, spec, params, lr, dev, kw):
     return res
 
 
+def consistency_main(a, spec, params, lr, dev, kw):
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.engine import downsample
+    from srmi.superres import RegionSuperResolver
+    r, s = a.overlaps[-1], spec.scale
+    Ks = sorted(set([0] + list(a.consistent)))
+    rs = {K: RegionSuperResolver(spec, params, tuple(lr.shape), (a.tile, a.tile), (r, r), device=dev,
+                                 graph=not a.no_graph, consistent=K, **kw) for K in Ks}
+
+    def rms(t):
+        return float(t.double().pow(2).mean().sqrt())
+
+    left = {}
+    for K in Ks:
+        for _ in range(a.warmup):
+            out = rs[K].super_resolve(lr)
+        torch.cuda.synchronize()
+        if not bool(torch.isfinite(out["model"]).all()):
+            raise SystemExit(f"superres_bench: consistent {K}: non-finite output")
+        left[K] = {"rms_D_model_minus_input": rms(downsample(out["model"][None], s, mode=rs[K].dmode)[0] - lr)}
+        if K:
+            left[K].update(rms_residual=rms(out["residual"]), rms_residual_left=rms(out["residual_left"]))
+    st = torch.cuda.current_stream()
+    ms = {K: [] for K in Ks}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for K in Ks:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(a.regions):
+                rs[K].super_resolve(lr)
+            e1.record(st)
+            e1.synchronize()
+            ms[K].append(e0.elapsed_time(e1) / a.regions)
+    mpix = (a.side * s) ** 2 / 1e6
+    res = {"tool": "superres_bench --consistent", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 super_resolve, 1 var, {a.side}^2 LR region -> {a.side * s}^2 HR, LR "
+                                  f"tile {a.tile}, overlap {r}", "graph": not a.no_graph, "warmup": a.warmup,
+                      "repeats": a.repeats, "regions_per_window": a.regions,
+                      "downsample": rs[0].dmode, "upsample": rs[0].umode,
+                      "weights": "default_init_ (untrained): the residuals and RMSEs describe THIS network, not a "
+                                 "trained one; no pass / fail bar"},
+           "hr_mpix_per_region": round(mpix, 3), "consistent": {}}
+    for K in Ks:
+        med = statistics.median(ms[K])
+        ratios = [x / y for x, y in zip(ms[K], ms[0])]  # per pair of neighbouring windows
+        res["consistent"][str(K)] = dict(
+            ms_per_region=round(med, 3), ms_min_max=[round(min(ms[K]), 3), round(max(ms[K]), 3)],
+            hr_mpix_per_s=round(mpix / (med * 1e-3), 2),
+            t_over_t0={"median": round(statistics.median(ratios), 4), "min_max": [round(min(ratios), 4),
+                                                                                  round(max(ratios), 4)]}, **left[K])
+    # a synthetic truth through score: the RMSE of every arm (before the eager timing below rewrites 'model')
+    hr = torch.tensor(synthetic_hr(1, 1, a.side * s, 98)[0]).to(dev)
+    res["truth"] = {}
+    for K in Ks:
+        images, losses = rs[K].score(hr)
+        res["truth"][str(K)] = {"rmse_model": float(losses["model"]),
+                                "rmse_interpolated": float(losses["interpolated"])}
+    Kmax = Ks[-1]
+    if Kmax > 0:  # the added launches, eager, on the largest K's buffers (each call corrects 'model' once more)
+        t = timed(rs[Kmax]._correct)
+        nbytes = 3.0 * lr.shape[0] * (a.side * s) ** 2 * 4
+        res["new_launches"] = {"K": Kmax, "launches": Kmax + 2, "ms": round(t, 4), "bytes_model": int(nbytes),
+                               "gb_per_s": round(nbytes / (t * 1e-3) / 1e9, 1),
+                               "share_of_region": round(t / statistics.median(ms[Kmax]), 5)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=1024, help="LR region side")
@@ -301,17 +380,20 @@ def main():
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
     ap.add_argument("--ensemble", type=int, nargs="+", default=None, metavar="K", choices=(1, 4, 8),
                     help="time RegionSuperResolver(ensemble=K) for each K (1 is always among them)")
+    ap.add_argument("--consistent", type=int, nargs="+", default=None, metavar="K", choices=range(17),
+                    help="time RegionSuperResolver(consistent=K) for each K (0 is always among them)")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
-                                                "spectra_bench.json, ensemble_bench.json)")
+                                                "spectra_bench.json, ensemble_bench.json, consistency_bench.json)")
     a = ap.parse_args()
-    if sum(x is not None for x in (a.land, a.spectra, a.ensemble)) > 1:
-        raise SystemExit("superres_bench: --land, --spectra and --ensemble are separate runs")
+    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) > 1:
+        raise SystemExit("superres_bench: --land, --spectra, --ensemble and --consistent are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
                              "spectra_bench.json" if a.spectra is not None else
-                             "ensemble_bench.json" if a.ensemble is not None else "superres_bench.json")
+                             "ensemble_bench.json" if a.ensemble is not None else
+                             "consistency_bench.json" if a.consistent is not None else "superres_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("superres_bench: no GPU (there is no CPU path to time)")
     from oracle.rcan_oracle import synthetic_hr
@@ -327,10 +409,11 @@ def main():
     default_init_(params, table, 0)
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
-    if a.land is not None or a.spectra is not None or a.ensemble is not None:
+    if a.land is not None or a.spectra is not None or a.ensemble is not None or a.consistent is not None:
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
-                          ensemble_main(a, spec, params, lr, dev, kw))
+                          ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
+                          consistency_main(a, spec, params, lr, dev, kw))
         print(line)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
