@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "common.hpp"
 #include "conv64_body.hpp"
@@ -236,28 +237,31 @@ constexpr int NGP = 2 * GD + 2 * GX;                             // groups per p
 
 
 
-// The body is instantiated once per wave (WV = wave index): the wave's DMA groups,
-// taps and tile rotation are compile-time constants (no SGPR pressure, no branches).
+// Eight waves, two per SIMD: the 36 N tiles are split 4 / 5 between waves w and w + 4
+// (the same SIMD: 17 + 20 MFMAs per K-step); waves 0-3 (the main role) also issue the
+// DMA and the bias gradient; every wave keeps all four output-channel tiles and writes
+// its partial slab in the layout of a 4-wave split (wave J / 9, tile J % 9), so
+// wgrad_reduce is unchanged.
 //
-// NW = 8 (two waves per SIMD): the 36 N tiles are split 4 / 5 between waves WV and
-// WV + 4 (the same SIMD: 17 + 20 MFMAs per K-step, as one 4-wave wave's 37); waves
-// 0-3 also issue the DMA (the 4-wave schedule) and the bias gradient; every wave
-// keeps all four output-channel tiles and writes its partial slab in the 4-wave
-// layout, so wgrad_reduce is unchanged.
+// The body is instantiated once per role (MAIN: waves 0-3, NT = 4; else waves 4-7, NT =
+// 5), not once per wave: the wave index wv is a run-time, wave-uniform value (an SGPR),
+// and what hangs on it -- the first N tile J0 with its taps, the tile rotation, the DMA
+// groups k = wave + 4 m, the vmcnt counts, the slab addresses -- is scalar arithmetic
+// done once outside the pair loop.  The four waves of a role share one pair loop in the
+// instruction cache instead of looping over disjoint code each.
 // DUG: the instantiation that may form du from g (p.gx, the fused conv2 backward only): the
 // others carry none of its code (F1's launch had 20 SGPR spills with it compiled in)
-template <int WV, int NW = 4, bool DUG = false>
-__device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, int chunk, int cb) {
+template <bool MAIN, bool DUG = false>
+__device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, int chunk, int cb, int wv) {
   using namespace v4;
-  static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   constexpr int NCA = 4;  // output-channel (A) tiles of every wave
-  // N tiles of this wave and its first one (8 waves: the younger half, waves 4-7, takes 5)
-  constexpr int NT = NW == 4 ? 9 : (WV < 4 ? 4 : 5);
-  constexpr int J0 = NW == 4 ? 9 * WV : (WV < 4 ? 4 * WV : 16 + 5 * (WV - 4));
-  constexpr bool kMain = WV < 4;  // DMA + bias gradient
+  // N tiles of this wave and its first one (the younger half, waves 4-7, takes 5)
+  constexpr int NT = MAIN ? 4 : 5;
+  const int J0 = MAIN ? 4 * wv : 16 + 5 * (wv - 4);  // (uniform)
+  constexpr bool kMain = MAIN;  // DMA + bias gradient
   constexpr bool kBias = kMain;
   const int tid = threadIdx.x, lane = tid & 63;
-  constexpr int wave = WV & 3, wave_s = WV & 3;
+  const int wave = wv & 3, wave_s = wave;  // (uniform: wv comes from readfirstlane)
   // chunk = (image, row band, 48-column block): W may be any multiple of 48 (the
   // upsampler's second stage runs at 96); Wd = the row stride in pixels
   const int Hr = p.H / p.row_splits, Wd = p.W, nxb = Wd / TW;
@@ -278,47 +282,44 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
   const int cl0 = ls ^ (((dq >> 1) & 1) << 1);   // g even
   const int cl1 = cl0 ^ 4;                         // g odd
 
-  // one DMA group: k < 2*GD -> dY row 2P + k / GD; else input row 2P + 1 + rr
-  // (pre = true: input rows -1 and 0 of the chunk, k < 2*GX)
-  auto dma = [&](int P, int k, bool pre) __attribute__((always_inline)) {
-    if (!pre && k < 2 * GD) {
-      const int rr = k / GD, g = k - rr * GD;
-      const int r = 2 * P + rr, y = ybase + r, xx = 8 * g + dq;
-      const int c = (g & 1) ? cl1 : cl0;
-      const bf16_t* src = plain
-                              ? dyn + ((size_t)y * Wd + xx) * Cout + c * 8
-                              : dyn + ((size_t)(2 * y + (cb >> 1)) * (2 * Wd) + 2 * xx + (cb & 1)) * 64 + c * 8;
-      glds16(src, lds0 + (uint32_t)((r % RD) * DSLOT + g * 1024));
-    } else {
-      const int kk = pre ? k : k - 2 * GD, rr = kk / GX, g = kk - rr * GX;
-      const int r = pre ? rr - 1 : 2 * P + 1 + rr;  // chunk-relative input row
-      const int y = ybase + r, hx = 8 * g + dq, xx = hx - 1;
-      const bool ok = hx < TW + 2 && y >= 0 && y < H && x0 + xx >= 0 && x0 + xx < Wd;
-      const int c = (g & 1) ? cl1 : cl0;
-      const void* src = ok ? (const void*)(xn + ((ptrdiff_t)y * Wd + xx) * 64 + c * 8) : zpage;
-      glds16(src, lds0 + (uint32_t)(DY_RING + ((r + 1) % RX) * XSLOT + g * 1024));
-    }
+  // one DMA group of the prologue: input rows -1 and 0 of the chunk, k < 2*GX
+  auto dma_pre = [&](int k) __attribute__((always_inline)) {
+    const int rr = k >= GX ? 1 : 0, g = k - rr * GX;  // (uniform)
+    const int r = rr - 1;                             // chunk-relative input row
+    const int y = ybase + r, hx = 8 * g + dq, xx = hx - 1;
+    const bool ok = hx < TW + 2 && y >= 0 && y < H && x0 + xx >= 0 && x0 + xx < Wd;
+    const int c = (g & 1) ? cl1 : cl0;
+    const void* src = ok ? (const void*)(xn + ((ptrdiff_t)y * Wd + xx) * 64 + c * 8) : zpage;
+    glds16(src, lds0 + (uint32_t)(DY_RING + ((r + 1) % RX) * XSLOT + g * 1024));
   };
   // Pair DMA with precomputed per-lane offsets: group m of this wave is k = wave + 4m
-  // (m < 7: waves 0,1 own 7 groups of a pair, waves 2,3 own 6).  Everything that
-  // does not change from pair to pair -- the lane's pixel, chunk and x validity --
-  // is computed once; per pair only a uniform base pointer and one add remain.
+  // (m < 7: waves 0,1 own 7 groups of a pair, waves 2,3 own 6).  Whatever the wave,
+  // groups m = 0..2 are dY groups (k < 2 GD = 12) and m = 3..5 input groups; only m = 6
+  // (k = 24 + wave < NGP = 26) exists for waves 0 and 1 alone.  Everything that does not
+  // change from pair to pair -- the lane's pixel, chunk and x validity, the group's row
+  // and place inside its ring slot (gofs, uniform) -- is computed once; per pair only
+  // two uniform bases and one add remain.
+  static_assert(GD == 6 && GX == 7 && NGP == 26, "the static dY / input split of the groups m");
+  const bool has6 = wave_s < 2;  // (uniform)
   int loff[7];
-  uint32_t okx = 0;
+  uint32_t gofs[7];  // rr * (slot pitch) + g * 1024: the ring slots of rows 2P, 2P+1 are adjacent
+  uint32_t okx = 0, rr1 = 0;  // bit m: x validity (lane) / the group's row rr (uniform)
 #pragma unroll
   for (int m = 0; m < 7; ++m) {
     const int k = wave_s + 4 * m;
-    loff[m] = 0;
-    if (k < 2 * GD) {
-      const int rr = k / GD, g = k - rr * GD, xx = 8 * g + dq;
+    if (m < 3) {
+      const int rr = k >= GD ? 1 : 0, g = k - rr * GD, xx = 8 * g + dq;
       const int c = (g & 1) ? cl1 : cl0;
       loff[m] = plain ? (rr * Wd + xx) * Cout + c * 8 : (2 * rr * (2 * Wd) + 2 * xx) * 64 + c * 8;
-    } else if (k < NGP) {
-      const int kk = k - 2 * GD, rr = kk / GX, g = kk - rr * GX, hx = 8 * g + dq, xx = hx - 1;
+      gofs[m] = (uint32_t)(rr * DSLOT + g * 1024);
+    } else {
+      const int kk = k - 2 * GD, rr = kk >= GX ? 1 : 0, g = kk - rr * GX, hx = 8 * g + dq, xx = hx - 1;
       const int c = (g & 1) ? cl1 : cl0;
-      const bool ok = hx < TW + 2 && x0 + xx >= 0 && x0 + xx < Wd;
+      const bool ok = hx < TW + 2 && x0 + xx >= 0 && x0 + xx < Wd && (m < 6 || has6);
       okx |= ok ? (1u << m) : 0u;
+      rr1 |= rr ? (1u << m) : 0u;
       loff[m] = (rr * Wd + (ok ? xx : 0)) * 64 + c * 8;
+      gofs[m] = (uint32_t)(DY_RING + rr * XSLOT + g * 1024);
     }
   }
   auto dma_pair_part = [&](int P, int m0, int m1) __attribute__((always_inline)) {
@@ -326,19 +327,18 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
                               : dyn + ((size_t)(2 * (ybase + 2 * P) + (cb >> 1)) * (2 * Wd) + (cb & 1)) * 64;
     const bf16_t* xb = xn + (ptrdiff_t)(ybase + 2 * P + 1) * Wd * 64;
     const bool yv0 = ybase + 2 * P + 1 < H, yv1 = ybase + 2 * P + 2 < H;
+    // dY row 2P + rr -> slot (2P + rr) & (RD-1) = ((2P) & (RD-1)) + rr; input row 2P+1+rr ->
+    // slot (row + 1) % RX = (2P + 2) % RX + rr (2P and RD, RX even: rr never wraps)
+    const uint32_t dbase = lds0 + (uint32_t)(((2 * P) & (RD - 1)) * DSLOT);
+    const uint32_t xbase = lds0 + (uint32_t)(((2 * P + 2) % RX) * XSLOT);
 #pragma unroll
     for (int m = m0; m < m1; ++m) {
-      const int k = wave_s + 4 * m;
-      if (k < 2 * GD) {
-        const int rr = k / GD, g = k - rr * GD;
-        glds16(dyb + loff[m], lds0 + (uint32_t)(((2 * P + rr) & (RD - 1)) * DSLOT + g * 1024));
-      } else if (k < NGP) {
-        const int kk = k - 2 * GD, rr = kk / GX, g = kk - rr * GX;
-        const bool ok = ((okx >> m) & 1u) && (rr ? yv1 : yv0);
+      if (m < 3) {
+        glds16(dyb + loff[m], dbase + gofs[m]);
+      } else if (m < 6 || has6) {
+        const bool ok = ((okx >> m) & 1u) && (((rr1 >> m) & 1u) ? yv1 : yv0);
         const void* src = ok ? (const void*)(xb + loff[m]) : zpage;
-        int slot = 2 * P + 2 + rr;  // input row 2P+1+rr -> slot (row + 1) % RX
-        slot = slot % RX;
-        glds16(src, lds0 + (uint32_t)(DY_RING + slot * XSLOT + g * 1024));
+        glds16(src, xbase + gofs[m]);
       }
     }
   };
@@ -375,17 +375,18 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
 
   // slot offsets: dY row r -> slot r & (RD-1); input row r -> slot (r + 1) % RX.
   // Per pair the lane's A row is 2j + prow, its B rows 2j + prow + ky (ky of tap t).
-  int boffr[NT];
+  // (ky is a run-time value of the wave, so every N tile has its own row offset; kept in
+  //  bytes, and the ring's wrap taken as an unsigned minimum: x - ring < x only past its end)
+  uint32_t boffr[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) boffr[t] = prow + bky[t];  // 0..3
+  for (int t = 0; t < NT; ++t) boffr[t] = (uint32_t)((prow + bky[t]) * XSLOT);  // 0..3 slots
   auto slots = [&](int j, uint32_t& ra, uint32_t (&rb)[NT]) __attribute__((always_inline)) {
     ra = (uint32_t)(((2 * j + prow) & (RD - 1)) * DSLOT);
-    int sb = (2 * j) % RX;  // uniform
+    const uint32_t sb = (uint32_t)(((2 * j) % RX) * XSLOT);  // uniform
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      int sl = sb + boffr[t];
-      sl = sl >= RX ? sl - RX : sl;
-      rb[t] = (uint32_t)(sl * XSLOT);
+      const uint32_t x = sb + boffr[t];
+      rb[t] = min(x, x - (uint32_t)(RX * XSLOT));
     }
   };
   auto load_a = [&](uint32_t ra, int kc, bf16x8 (&a)[NCA]) __attribute__((always_inline)) {
@@ -407,20 +408,23 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
     for (int t = 0; t < NT; ++t)
       b[t] = cat_tr(lds_tr(smem, rb[t] + bcol[t][0] + kc * 2048), lds_tr(smem, rb[t] + bcol[t][1] + kc * 2048));
   };
-  // vmcnt helper: this wave owns 7 (waves 0,1) or 6 (waves 2,3) groups of a pair
-  auto wait_groups = [&](int full_pairs, int extra) __attribute__((always_inline)) {
-    const int n = full_pairs * (wave_s < 2 ? 7 : 6) + extra;
-    if (n >= 14) wait_vm<14>();
-    else if (n == 13) wait_vm<13>();
-    else if (n == 12) wait_vm<12>();
-    else if (n == 11) wait_vm<11>();
-    else if (n == 10) wait_vm<10>();
-    else if (n == 9) wait_vm<9>();
-    else if (n == 7) wait_vm<7>();
-    else if (n == 6) wait_vm<6>();
-    else if (n == 5) wait_vm<5>();
-    else wait_vm<0>();
+  // vmcnt helper: FP whole pairs and EX more groups of this wave may stay in flight; the wave
+  // owns 7 (waves 0,1) or 6 (waves 2,3) groups of a pair, so the count is one of two
+  // immediates behind one uniform branch.  Waves 4-7 issue no DMA and wait for none.
+  auto wait_groups = [&](auto fp, auto ex) __attribute__((always_inline)) {
+    constexpr int FP = decltype(fp)::value, EX = decltype(ex)::value;
+    static_assert(FP * 7 + EX <= 14, "vmcnt counts in use");
+    if constexpr (kMain) {
+      if (has6) wait_vm<FP * 7 + EX>();
+      else wait_vm<FP * 6 + EX>();
+    }
   };
+  using std::integral_constant;
+  constexpr integral_constant<int, 0> i0{};
+  constexpr integral_constant<int, 1> i1{};
+  constexpr integral_constant<int, 2> i2{};
+  constexpr integral_constant<int, 3> i3{};
+  constexpr integral_constant<int, 5> i5{};
 
   // (gx_s: dy is the gradient stream g) du = bf16(g s + dm / HW) formed in place on this
   // wave's own dY groups of a pair once they landed, before the barrier that publishes
@@ -444,16 +448,16 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
     uint4 v[3];
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
-      const int k = wave_s + 4 * m, rr = k / GD, g = k - rr * GD;
-      q[m] = reinterpret_cast<uint4*>(smem + ((2 * P + rr) & (RD - 1)) * DSLOT + g * 1024 + lane * 16);
+      // (the group's place as in dma_pair_part: slot (2P) & (RD-1) plus gofs)
+      q[m] = reinterpret_cast<uint4*>(smem + ((2 * P) & (RD - 1)) * DSLOT + gofs[m] + lane * 16);
       v[m] = *q[m];
     }
 #pragma unroll
     for (int m = 0; m < 3; ++m) *q[m] = du_from_g8(v[m], sv, mv);
   };
-  // the image's CALayer backward MLP (ca_bwd.hpp) by waves 4-7 (8 waves), which issue no
+  // the image's CALayer backward MLP (ca_bwd.hpp) by waves 4-7, which issue no
   // DMA: the compiler's wait for its operands then drains no DMA group of the prologue
-  const int mt = NW == 8 ? tid - 256 : tid;  // MLP thread
+  const int mt = tid - 256;  // MLP thread
   CaBwdPre cbq;
   if (gx && mt >= 0) {
     if (p.gx.mlp) {
@@ -468,7 +472,7 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
   if constexpr (kMain) {
 #pragma unroll
     for (int m = 0; m < 4; ++m)
-      if (wave_s + 4 * m < 2 * GX) dma(0, wave_s + 4 * m, true);
+      if (m < 3 || has6) dma_pre(wave_s + 4 * m);  // (k = 12 + wave < 2 GX = 14: waves 0, 1)
     for (int P = 0; P < PF && P < np; ++P) dma_pair_part(P, 0, 7);
   }
   if (gx) {
@@ -479,7 +483,10 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
     }
     __syncthreads();  // (the table)
   }
-  wait_groups(min(PF, np) - 1, 0);
+  static_assert(PF == 3, "the pairs of the prologue");
+  if (np >= 3) wait_groups(i2, i0);
+  else if (np == 2) wait_groups(i1, i0);
+  else wait_groups(i0, i0);
   if constexpr (kMain) {
     if (gx) gx_pair(0);
   }
@@ -487,10 +494,11 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
   WSTAMP(1);
 
   // fragments double-buffered across K-steps; a pair has 3 K-steps, so the pair loop
-  // is unrolled by two (np is even) to keep the buffer parity compile-time.  8 waves
-  // (256 registers a wave): B single-buffered, each tile reloaded right behind its
-  // MFMAs (the partner wave on the SIMD covers the read latency).
-  constexpr int NB = NW == 8 ? 1 : 2;
+  // is unrolled by two (an odd np leaves after the first half of its last round) to
+  // keep the buffer parity compile-time.  B is single-buffered (256 registers a wave),
+  // each tile reloaded right behind its MFMAs (the partner wave on the SIMD covers the
+  // read latency).
+  constexpr int NB = 1;
   bf16x8 A[2][NCA], B[NB][NT];
   uint32_t ra, rb[NT];
   slots(0, ra, rb);
@@ -501,6 +509,7 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int j = j0 + q;
+      if (q && j >= np) break;  // (uniform)
       WSTAMP(2 + min(j, 59));
       const bool pf = j + PF < np;
       const bool more = j + 1 < np;
@@ -513,22 +522,15 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
           dma_pair_part(j + PF, kc == 0 ? 0 : (kc == 1 ? 3 : 5), kc == 0 ? 3 : (kc == 1 ? 5 : 7));
         __builtin_amdgcn_sched_barrier(0);
         const bool ld = kc < 2 || more;
-        if constexpr (NB == 2) {
-          if (kc < 2) load_step(ra, rb, kc + 1, A[nxt], B[nxt]);
-          else if (more) load_step(ran, rbn, 0, A[nxt], B[nxt]);  // next pair's first K-step
-        } else {
-          if (kc < 2) load_a(ra, kc + 1, A[nxt]);
-          else if (more) load_a(ran, 0, A[nxt]);
-        }
+        if (kc < 2) load_a(ra, kc + 1, A[nxt]);
+        else if (more) load_a(ran, 0, A[nxt]);  // next pair's first K-step
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-          for (int ct = 0; ct < NCA; ++ct) acc[ct][t] = mfma16(A[cur][ct], B[cur % NB][t], acc[ct][t]);
+          for (int ct = 0; ct < NCA; ++ct) acc[ct][t] = mfma16(A[cur][ct], B[0][t], acc[ct][t]);
         if constexpr (kBias) bacc = mfma16(A[cur][0], ones, bacc);  // slot 0 = this wave's own co tile
-        if constexpr (NB == 1) {
-          if (kc < 2) load_b(rb, kc + 1, B[0]);
-          else if (more) load_b(rbn, 0, B[0]);
-        }
+        if (kc < 2) load_b(rb, kc + 1, B[0]);
+        else if (more) load_b(rbn, 0, B[0]);
         // the next K-step's transposed reads issued behind the MFMAs, one per MFMA
         constexpr int NRD = 2 * (NCA + NT), NMF = NCA * NT + (kBias ? 1 : 0);
         constexpr int NPAIR = NRD < NMF ? NRD : NMF;
@@ -546,16 +548,18 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
           // (gx) du of pair j+1 behind K-step 0's MFMAs: in flight may stay pair j+2 and the
           // 3 groups of pair j+PF issued above; the barrier of K-step 1 publishes it
           if (kc == 0 && gx && more) {
-            if (j + 2 < np) wait_groups(1, pf ? 3 : 0);
-            else wait_groups(0, 0);
+            if (j + 2 >= np) wait_groups(i0, i0);
+            else if (pf) wait_groups(i1, i3);
+            else wait_groups(i1, i0);
             gx_pair(j + 1);
           }
         }
         if (kc == 1) {
           // pair j+1 must have landed before K-step 2 reads its first fragments.  In
           // flight may stay: pair j+2 (whole) and the 5 groups of pair j+PF issued above.
-          if (j + 2 < np) wait_groups(1, pf ? 5 : 0);
-          else wait_groups(0, 0);
+          if (j + 2 >= np) wait_groups(i0, i0);
+          else if (pf) wait_groups(i1, i5);
+          else wait_groups(i1, i0);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
@@ -574,7 +578,8 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
   // left in the flush at its end (a standalone wgrad + reduce pair measured the
   // other way round in round 2: the launch 0.9 us shorter, the reduce 1.9 us longer)
   // (N tile J, slot ct of rotation `wave`) -> the 4-wave position (wave J / 9, tile
-  // J % 9, the slot of the same output-channel tile under that wave's rotation)
+  // J % 9, the slot of the same output-channel tile under that wave's rotation): scalar
+  // arithmetic on the run-time J0
   const size_t soff = (size_t)chunk * Cout * 576 + (size_t)cb * (64 * 576);
   // (write-through: the slab leaves the XCD's L2 while the other waves still
   //  compute, instead of in the dirty-line flush at the end of the launch)
@@ -602,24 +607,13 @@ __device__ __forceinline__ void wgrad48_body(const WgradParams& p, char* smem, i
   WSTAMP(63);
 }
 
-template <int NW = 4, bool DUG = false>
+// one branch on the role; the wave index stays a run-time SGPR value inside it
+template <int NW, bool DUG = false>
 __device__ __forceinline__ void wgrad48_dispatch(const WgradParams& p, char* smem, int chunk, int cb) {
-  switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-    case 0: wgrad48_body<0, NW, DUG>(p, smem, chunk, cb); break;
-    case 1: wgrad48_body<1, NW, DUG>(p, smem, chunk, cb); break;
-    case 2: wgrad48_body<2, NW, DUG>(p, smem, chunk, cb); break;
-    case 3: wgrad48_body<3, NW, DUG>(p, smem, chunk, cb); break;
-    default:
-      if constexpr (NW == 8) {
-        switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-          case 4: wgrad48_body<4, NW, DUG>(p, smem, chunk, cb); break;
-          case 5: wgrad48_body<5, NW, DUG>(p, smem, chunk, cb); break;
-          case 6: wgrad48_body<6, NW, DUG>(p, smem, chunk, cb); break;
-          default: wgrad48_body<7, NW, DUG>(p, smem, chunk, cb); break;
-        }
-      }
-      break;
-  }
+  static_assert(NW == 8, "two waves per SIMD: waves w and w + 4 split a SIMD's N tiles");
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wv < 4) wgrad48_body<true, DUG>(p, smem, chunk, cb, wv);
+  else wgrad48_body<false, DUG>(p, smem, chunk, cb, wv);
 }
 
 constexpr int kWgradNW = 8;  // waves per workgroup of the standalone filter gradient (two per SIMD)
@@ -666,16 +660,16 @@ __global__ void __launch_bounds__(NW * 64, 1) rcab_bwd_kernel(ConvParams cp, int
     if (c1 > c0) conv = c0;
     else w = b - c0;
   }
-  if (conv >= 0) {
-    conv64_body<48, EPI, NW>(cp, run_len, conv, smem, tail, false);
-    return;
-  }
-  const int nch = wp.N * wp.row_splits;
-  if (tail > 0) {
-    conv64_body<48, EPI, NW>(cp, run_len, w, smem, tail, true);
+  // one copy of the dgrad body in the code object: a dgrad workgroup runs its run's strips
+  // (but the last `tail`), a filter-gradient workgroup the `tail` strips of its run first
+  const bool tail_part = conv < 0;  // (uniform)
+  if (!tail_part || tail > 0) {
+    conv64_body<48, EPI, NW>(cp, run_len, tail_part ? w : conv, smem, tail, tail_part);
+    if (!tail_part) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // every wave is past its last LDS access of the strips
   }
+  const int nch = wp.N * wp.row_splits;
   wgrad48_dispatch<NW, EPI == EPI_DG_RELUMASK>(wp, smem, w % nch, w / nch);
 }
 
@@ -758,7 +752,7 @@ int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradPara
 
 
 static bool use_wgrad48(const WgradParams& p) {
-  // v4 (row-pair rings, per-wave specialised) for W a multiple of 48: one chunk per
+  // v4 (row-pair rings, one body per wave role) for W a multiple of 48: one chunk per
   // (image, row band, 48-column block)
   return !p.f32 && p.W % 48 == 0 && p.row_splits > 0 && (p.H / p.row_splits) % 2 == 0;
 }
@@ -770,7 +764,9 @@ int wgrad3x3_slab_layout(const WgradParams& p) { return use_wgrad48(p) ? 1 : 0; 
 int wgrad3x3_launch(const WgradParams& p, hipStream_t st) {
   if (p.gx.rec) return SRMI_ERR_ARG;  // (du formed from g: the fused backward launch only)
   if (p.f32) return wgrad_f32_launch(p, st);
-  if (p.Cout % 64 || p.H % p.row_splits || (p.H / p.row_splits) % 4) return SRMI_ERR_SHAPE;
+  // rows per chunk: whole row pairs (wgrad48_kernel) or whole 4-row stages (wgrad3x3_kernel)
+  if (p.Cout % 64 || p.row_splits <= 0 || p.H % p.row_splits || (p.H / p.row_splits) % (use_wgrad48(p) ? 2 : 4))
+    return SRMI_ERR_SHAPE;
   if (p.dy_mode == IN_UNSHUF && p.Cout != 256) return SRMI_ERR_SHAPE;
   if (!slab_range_ok(p, wgrad3x3_nslabs(p))) return SRMI_ERR_SHAPE;
   dim3 grid(wgrad3x3_nslabs(p), p.Cout / 64);
