@@ -60,6 +60,11 @@
  *   srmi_spectra                 -> windowed radial power spectra of a prediction against
  *                                   a truth.  No reference counterpart: the reference
  *                                   scores a field by its RMSE alone.
+ *   srmi_ssim_workspace,
+ *   srmi_ssim                    -> Gaussian-window SSIM of a prediction against a truth,
+ *                                   with its per-pixel map, and the mean square error that
+ *                                   PSNR needs.  No reference counterpart: the reference
+ *                                   scores a field by its RMSE alone.
  *   srmi_spectral_loss_workspace,
  *   srmi_spectral_loss_parts,
  *   srmi_spectral_loss_from_parts,
@@ -614,6 +619,50 @@ int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int ki
 int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
 int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
                  size_t workspace_bytes, float* out, int* nused, void* stream);
+
+/* ---- the SSIM score (no reference counterpart) -------------------------- */
+/* Structural similarity (Wang, Bovik, Sheikh, Simoncelli 2004, Gaussian form: scikit-image's
+ * structural_similarity(gaussian_weights=True, use_sample_covariance=False)) of a
+ * (prediction) against b (truth), both [C][H][W] fp32 on the device, possibly with NaN / Inf,
+ * per channel; tests/ssim_oracle.py restates it in numpy.
+ *   Window: 11 taps g[k] ~ exp(-(k - 5)^2 / (2 1.5^2)), normalised to sum 1 in fp64 and then
+ *   rounded to fp32; G = g (x) g.  Only VALID positions are evaluated, 5 <= y < H - 5 and
+ *   5 <= x < W - 5: there is no padding.
+ *   Mask: a position is USED, for that channel, iff all 121 pixels of its window are finite
+ *   in a and in b in that channel.  The decision is per channel (srmi_spectra skips a window
+ *   for all channels; this score does not).  One NaN removes exactly the 121 positions whose
+ *   window holds it.
+ *   Range and pivot: lo, hi = the min and max of b's finite pixels in the channel; L = hi - lo
+ *   (fp32), or data_range for every channel where data_range > 0; the pivot r = 0.5 lo +
+ *   0.5 hi (fp32) is always b's.  All moments are formed on a - r and b - r (fp32): variances
+ *   and the covariance do not change with the shift and the means get r added back.  The
+ *   pivot is part of the definition: ocean fields sit at 290 +- 1.5, where E[x^2] - mu^2
+ *   without it loses the variance in fp32.  min and max do not depend on the order of the
+ *   reduction, so r and L are exact and reproducible.
+ *   Quantities: mu_a = G * a, mu_b = G * b, s_aa = G * a^2 - mu_a^2, s_bb likewise, s_ab =
+ *   G * (a b) - mu_a mu_b; C1 = (0.01 L)^2, C2 = (0.03 L)^2;
+ *   cs = (2 s_ab + C2) / (s_aa + s_bb + C2), ssim = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1)
+ *   * cs, in fp32: the horizontal pass, then the vertical one, taps in ascending order.
+ * out [C][4] fp32 = {the mean of ssim over the used positions, the mean of cs over them,
+ * mse = the mean of (a - b)^2 over the pixels finite in both (every pixel of the plane, the
+ * border included; the difference and its square in fp64), L}; count [C][2] int64 = {nwin,
+ * the used positions; npix, the pixels of mse}.  The sums are fp64 per workgroup and over
+ * the workgroups, in a fixed order, no atomics: bit-identical from run to run, exact counts
+ * at 4096^2 and beyond.  nwin == 0 or npix == 0 gives the IEEE 0 / 0 = NaN; a channel of b
+ * without a finite pixel has L = NaN.
+ * map, when not NULL, [C][H][W] fp32: ssim at the used positions and the canonical NaN
+ * (0x7fc00000) everywhere else -- the 5-pixel border and the positions not used.  Every
+ * element is written.  out and count do not depend on whether map is given.
+ * Any C in 1 .. 65535 and H, W >= 11 with H W < 2^31; no alignment requirement on a, b or
+ * map.  srmi_ssim_workspace (host only) gives the bytes of `workspace` (16-byte aligned; it
+ * need not be initialised): five partial sums per 24 x 64 rectangle of every plane and the
+ * min / max pairs.  Three launches on `stream`; no host synchronisation, no allocation:
+ * capturable.  data_range NaN or +-Inf (<= 0 means "from the truth"), a missing a, b,
+ * workspace, out or count, a workspace that is too small, H or W below 11, C below 1:
+ * SRMI_ERR_ARG, and nothing is launched. */
+int srmi_ssim_workspace(int C, int H, int W, size_t* bytes);
+int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_range, void* workspace,
+              size_t workspace_bytes, float* out, long long* count, float* map, void* stream);
 
 /* ---- consistency with the coarse input (no reference counterpart) -------- */
 /* Iterative back-projection x <- x + U(lr - D x) of an HR field x [C][h s][w s] onto the LR

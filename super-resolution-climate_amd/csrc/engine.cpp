@@ -1628,6 +1628,13 @@ int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int
   return spectra_launch(a, b, C, H, W, P, Q, workspace, workspace_bytes, out, nused, S_(stream));
 }
 
+int srmi_ssim_workspace(int C, int H, int W, size_t* bytes) { return ssim_workspace(C, H, W, bytes); }
+
+int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_range, void* workspace,
+              size_t workspace_bytes, float* out, long long* count, float* map, void* stream) {
+  return ssim_launch(a, b, C, H, W, data_range, workspace, workspace_bytes, out, count, map, S_(stream));
+}
+
 int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
   return spectral_loss_workspace(nplanes, H, W, P, Q, bytes);
 }

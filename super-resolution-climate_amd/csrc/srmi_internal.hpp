@@ -324,6 +324,10 @@ int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int fl
 int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
 int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
                    float* out, int* nused, hipStream_t st);
+// the SSIM / PSNR score: Gaussian-window structural similarity of two fields (ssim.hip)
+int ssim_workspace(int C, int H, int W, size_t* bytes);
+int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_range, void* ws, size_t ws_bytes,
+                float* out, long long* count, float* map, hipStream_t st);
 // the spectral loss term of the training step (spectral_loss.hip)
 int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
 int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,

@@ -279,6 +279,61 @@ def save_spectra(path: str, spectra: Dict[str, object], window: int, varnames: S
     return path
 
 
+SSIM_SCALARS = ("ssim", "cs", "mse", "psnr", "data_range")
+SSIM_COUNTS = ("nwin", "npix")
+
+
+def save_ssim(path: str, ssim: Dict[str, object], varnames: Sequence[str]) -> str:
+    """One SSIM score (the dict of srmi.ssim.SSIMScore.measure, e.g. one entry of
+    RegionSuperResolver.score_ssim's third result) as a netCDF-3 file, through the same scipy
+    writer: 'ssim', 'cs', 'mse', 'psnr', 'data_range' as float32 and 'nwin', 'npix' as float64
+    (netCDF-3 has no int64; a double holds every count below 2^53 exactly) on ('channel',),
+    'map' as float32 on ('channel', 'y', 'x') with ``_FillValue = NaN`` when the dict holds
+    it, and the attribute ``varnames`` (the channel names joined by ``,``, as loss_keys is).
+    No reference counterpart."""
+    from scipy.io import netcdf_file
+    missing = [k for k in SSIM_SCALARS + SSIM_COUNTS if k not in ssim]
+    if missing:
+        raise ValueError(f"ssim lacks {missing}")
+    n = len(varnames)
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        f.createDimension("channel", n)
+        for q in SSIM_SCALARS + SSIM_COUNTS:
+            dt = np.float32 if q in SSIM_SCALARS else np.float64
+            a = np.ascontiguousarray(_np(ssim[q]).astype(dt))
+            if a.shape != (n,):
+                raise ValueError(f"{q}: {a.shape} is not {(n,)}")
+            dv = f.createVariable(q, dt, ("channel",))
+            if q in SSIM_SCALARS:
+                dv._FillValue = np.array([np.nan], dtype=np.float32)
+            dv[:] = a
+        if "map" in ssim:
+            m = np.ascontiguousarray(_np(ssim["map"]).astype(np.float32))
+            if m.ndim != 3 or m.shape[0] != n:
+                raise ValueError(f"map: {m.shape} is not [{n}, H, W]")
+            f.createDimension("y", m.shape[1])
+            f.createDimension("x", m.shape[2])
+            mv = f.createVariable("map", np.float32, ("channel", "y", "x"))
+            mv._FillValue = np.array([np.nan], dtype=np.float32)
+            mv[:] = m
+    return path
+
+
+def load_ssim(path: str) -> Tuple[Dict[str, np.ndarray], List[str]]:
+    """The inverse of save_ssim: (the score as numpy arrays, the counts int64 again; varnames)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        out = {q: np.array(f.variables[q][:], dtype=np.float32) for q in SSIM_SCALARS}
+        out.update({q: np.array(f.variables[q][:]).astype(np.int64) for q in SSIM_COUNTS})
+        if "map" in f.variables:
+            out["map"] = np.array(f.variables["map"][:], dtype=np.float32)
+        return out, names.split(",") if names else []
+
+
 def load_spectra(path: str) -> Tuple[Dict[str, np.ndarray], int, List[str]]:
     """The inverse of save_spectra: (spectra as numpy arrays, window, varnames)."""
     from scipy.io import netcdf_file

@@ -344,6 +344,7 @@ class RegionSuperResolver:
         self.loss_i = torch.zeros(4, **f32)
         self._graph = None
         self._spectra = {}  # (window, stride) -> the SpectralScore of each image (score_spectra)
+        self._ssim = {}  # (data_range, maps) -> the SSIMScore of each image (score_ssim)
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -523,6 +524,32 @@ class RegionSuperResolver:
             self._spectra[key] = {name: SpectralScore((self.C, self.h * s, self.w * s), window, stride,
                                                       device=self.device) for name in ("model", "interpolated")}
         return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._spectra[key].items()}
+
+    def score_ssim(self, hr_region: torch.Tensor, data_range: Optional[float] = None, maps: bool = False):
+        """``score``, then the SSIM / PSNR score (srmi.ssim.SSIMScore) of 'model' and of
+        'interpolated' against hr_region: (images, losses, {'model': ..., 'interpolated':
+        ...}), each entry the dict of SSIMScore.measure -- per channel 'ssim', 'cs' (the
+        contrast-structure factor, the number that falls when the output is too smooth),
+        'mse', 'psnr', 'data_range', 'nwin', 'npix' and, with maps=True, 'map' [C, s h, s w],
+        the per-pixel SSIM that belongs beside 'spread' and 'residual'.  data_range: L for
+        every channel; None takes each channel's max - min of hr_region.  images and losses
+        are ``score``'s, bit for bit; the entries are views valid until the next call with
+        the same data_range and maps.  No host synchronisation.  With graph=True the score
+        is measured after the replay, outside the captured graph.  ``ensemble`` and
+        ``consistent`` change 'model' and nothing in how it is scored.
+
+        land=True: the NaN of the image and of hr_region are the mask -- a position whose
+        11 x 11 window touches one is not used ('nwin' counts the rest, 'map' is NaN
+        there), so a coast costs a 5-pixel rim, not whole windows."""
+        from .ssim import SSIMScore
+        s = self.s
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        key = (None if data_range is None else float(data_range), bool(maps))
+        if key not in self._ssim:
+            self._ssim[key] = {name: SSIMScore((self.C, self.h * s, self.w * s), data_range, maps, device=self.device)
+                               for name in ("model", "interpolated")}
+        return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._ssim[key].items()}
 
     def set_params(self, params: torch.Tensor) -> None:
         """Load new weights: copied into the parameter buffer the engines (and the

@@ -35,6 +35,17 @@ baseline there is -- the time of the numpy oracle (tests/spectra_oracle.py, fp64
 host for the same two pairs of fields, run once, with the device's largest deviation from
 it; writes profiles/spectra_bench.json.
 
+--ssim: what does the SSIM / PSNR score cost?  One RegionSuperResolver at the last of
+--overlaps scores a synthetic HR truth: ``score``, ``score_ssim`` (with and without the
+maps) and the SSIM stage alone (SSIMScore.measure of 'model' and of 'interpolated' against
+the truth, with and without the map) alternate window by window on one device.  Reports the
+median and the spread of each, the stage's share of the ``score_ssim`` call and its time
+beside ``score``'s, the bytes the stage must move (a and b read once per measure, the map
+written when asked for) with the bytes/s that makes, the scores, and -- for context -- the
+time of the numpy oracle (tests/ssim_oracle.py, fp64 and fp32) on the host for the same two
+pairs of fields, run once, with the device's largest deviation from the fp64 oracle next to
+e32, the fp32 oracle's; writes profiles/ssim_bench.json.  No pass / fail bar.
+
 --ensemble K [K ...]: what does the self-ensemble cost, and what does it give?  One
 RegionSuperResolver(ensemble=K) per K in {1, 4, 8} (1 always among them) on the default
 region at the last of --overlaps, the arms alternating window by window.  Reports the HR
@@ -230,6 +241,92 @@ def spectra_main(a, spec, params, dev, kw):
     return res
 
 
+def ssim_main(a, spec, params, dev, kw):
+    import time
+
+    import numpy as np
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.ssim import SSIMScore
+    from srmi.superres import RegionSuperResolver
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ssim_oracle as so
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    hr = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    rs = RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                             graph=not a.no_graph, **kw)
+    for _ in range(a.warmup):
+        images, losses, ssim = rs.score_ssim(hr, maps=True)
+        rs.score_ssim(hr)
+    torch.cuda.synchronize()
+    names = ("model", "interpolated")
+    scorers = {True: rs._ssim[(None, True)], False: rs._ssim[(None, False)]}
+
+    def stage(maps):
+        for name in names:
+            scorers[maps][name].measure(images[name], hr)
+
+    runs = {"score": lambda: rs.score(hr), "score_ssim": lambda: rs.score_ssim(hr),
+            "score_ssim_maps": lambda: rs.score_ssim(hr, maps=True), "stage": lambda: stage(False),
+            "stage_maps": lambda: stage(True)}
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for k, fn in runs.items():
+            n = a.regions * (20 if k.startswith("stage") else 1)  # a window of the stage alone is many calls
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(n):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / n)
+    images, losses, ssim = rs.score_ssim(hr, maps=True)
+    torch.cuda.synchronize()
+    truth = hr.cpu().numpy()
+    host = {"float64": 0.0, "float32": 0.0}
+    dev_err, e32s, scores = {}, {}, {}
+    for name in names:
+        img = images[name].cpu().numpy()
+        t0 = time.perf_counter()
+        o64 = so.ssim(img, truth)
+        host["float64"] += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        o32 = so.ssim(img, truth, dtype=np.float32)
+        host["float32"] += time.perf_counter() - t0
+        got = ssim[name]["map"].cpu().numpy().astype(np.float64)
+        counts = (int(ssim[name]["nwin"].item()), int(ssim[name]["npix"].item()))
+        if counts != (int(o64["nwin"][0]), int(o64["npix"][0])):
+            raise SystemExit(f"superres_bench: {name}: counts differ from the oracle's")
+        dev_err[name] = float(np.nanmax(np.abs(got - o64["map"])))
+        e32s[name] = float(np.nanmax(np.abs(o32["map"].astype(np.float64) - o64["map"])))
+        scores[name] = {q: float(ssim[name][q]) for q in ("ssim", "cs", "psnr", "mse", "data_range")}
+        scores[name]["rmse_of_score"] = float(losses[name])
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    px = float(side) ** 2
+    nbytes = {"stage": 2 * 2 * 4 * px, "stage_maps": 2 * 3 * 4 * px}  # two measures: a, b read once (+ the map written)
+    sc0 = scorers[True]["model"]
+    res = {"tool": "superres_bench --ssim", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 score_ssim, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR tile "
+                                  f"{a.tile}, overlap {r}; two SSIM scores (model, interpolated) per call",
+                      "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                      "regions_per_window": a.regions, "stage_calls_per_window": a.regions * 20,
+                      "workspace_mib_per_score": round(sc0.workspace.numel() / 2 ** 20, 2)},
+           "ms": {k: {"median": round(med[k], 4), "min_max": [round(min(v), 4), round(max(v), 4)]}
+                  for k, v in ms.items()},
+           "stage_share_of_score_ssim": round(med["stage"] / med["score_ssim"], 5),
+           "stage_maps_share_of_score_ssim_maps": round(med["stage_maps"] / med["score_ssim_maps"], 5),
+           "stage_over_score": round(med["stage"] / med["score"], 5),
+           "score_ssim_over_score": round(med["score_ssim"] / med["score"], 4),
+           "stage_bytes": {k: int(v) for k, v in nbytes.items()},
+           "stage_gb_per_s": {k: round(v / (med[k] * 1e-3) / 1e9, 1) for k, v in nbytes.items()},
+           "scores": scores, "nwin": int(ssim["model"]["nwin"].item()),
+           "host_oracle_s": {k: round(v, 2) for k, v in host.items()},
+           "device_map_vs_oracle_max_abs": {k: float(f"{v:.3e}") for k, v in dev_err.items()},
+           "e32_map_max_abs": {k: float(f"{v:.3e}") for k, v in e32s.items()}}
+    return res
+
+
 def ensemble_main(a, spec, params, lr, dev, kw):
     from oracle.rcan_oracle import synthetic_hr
     from srmi.superres import RegionSuperResolver
@@ -378,20 +475,23 @@ def main():
                     help="paint a coast with about this share of dry pixels and compare land=True with land=False")
     ap.add_argument("--spectra", type=int, nargs="?", const=256, default=None, metavar="WINDOW",
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
+    ap.add_argument("--ssim", action="store_true", help="time score_ssim's SSIM stage beside score")
     ap.add_argument("--ensemble", type=int, nargs="+", default=None, metavar="K", choices=(1, 4, 8),
                     help="time RegionSuperResolver(ensemble=K) for each K (1 is always among them)")
     ap.add_argument("--consistent", type=int, nargs="+", default=None, metavar="K", choices=range(17),
                     help="time RegionSuperResolver(consistent=K) for each K (0 is always among them)")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
-                                                "spectra_bench.json, ensemble_bench.json, consistency_bench.json)")
+                                                "spectra_bench.json, ssim_bench.json, ensemble_bench.json, "
+                                                "consistency_bench.json)")
     a = ap.parse_args()
-    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) > 1:
-        raise SystemExit("superres_bench: --land, --spectra, --ensemble and --consistent are separate runs")
+    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim > 1:
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --ensemble and --consistent are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
                              "spectra_bench.json" if a.spectra is not None else
+                             "ssim_bench.json" if a.ssim else
                              "ensemble_bench.json" if a.ensemble is not None else
                              "consistency_bench.json" if a.consistent is not None else "superres_bench.json")
     if not torch.cuda.is_available():
@@ -409,9 +509,10 @@ def main():
     default_init_(params, table, 0)
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
-    if a.land is not None or a.spectra is not None or a.ensemble is not None or a.consistent is not None:
+    if a.land is not None or a.spectra is not None or a.ssim or a.ensemble is not None or a.consistent is not None:
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
+                          ssim_main(a, spec, params, dev, kw) if a.ssim else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
                           consistency_main(a, spec, params, lr, dev, kw))
         print(line)
