@@ -77,6 +77,11 @@
  *                                   coarse input, iterated in LR space.  No reference
  *                                   counterpart: the reference never starts from a coarse
  *                                   field.
+ *   srmi_consistency_adjoint_gather,
+ *   srmi_consistency_adjoint_iterate,
+ *   srmi_consistency_adjoint_apply -> the transpose of that correction, for training
+ *                                   through it as the model's last layer.  No reference
+ *                                   counterpart: the reference's networks are free regressors.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -706,6 +711,41 @@ int srmi_consistency_iterate(const float* r, const int* active, int C, int h, in
  * must be finite (srmi_consistency_iterate's is).  16-byte accesses where scale % 4 == 0
  * and hr is 16-byte aligned. */
 int srmi_consistency_apply(const float* R, int C, int h, int w, int scale, int umode, float* hr, void* stream);
+
+/* The adjoint of the correction, for training through it.  With M the active mask, G the
+ * clamped D U stencil above and E = M (I - G), the three calls above compute x_K = x0 + U P M
+ * (lr - D x0), P = sum_{k < K} E^k, which is affine in x0 with Jacobian J = I - U P M D.  For
+ * a gradient g [C][h s][w s] with respect to x_K, J^T g is
+ *     q = U^T g;   t_0 = q, t_{k+1} = (I - G^T)(M t_k), Q = sum_{k < K} t_k;   g0 = g - D^T (M Q)
+ * (lr takes no gradient).  The same conventions hold: C counts planes, fp32, on `stream`, no
+ * host synchronisation, no atomics, no allocation, a fixed summation order -- capturable and
+ * bit-identical from run to run -- and the same refusals, with nothing enqueued. */
+/* q [C][h][w] = U^T g: each LR cell sums the HR pixels whose clamped taps reach it (those of
+ * the blocks within 2 of it per axis, 1 for bilinear), with the weights of srmi_upsample /
+ * srmi_interpolate at that pixel, taps that clamp onto one cell added in ascending tap order.
+ * Separable: a workgroup owns a band of up to 8 LR rows and a strip of up to 64 LR columns,
+ * keeps the per-axis weights in an LDS table, reduces the band's HR rows along x into LDS
+ * (ascending X) and those along y (ascending Y).  Band and strip shrink until the LDS fits
+ * 48 KB (a band of one row and a strip of 8 columns at scale 64 take 31.6 KB), so there is no
+ * limit on w s.  16-byte loads of g where scale % 4 == 0 and g is 16-byte aligned.  g must be
+ * finite.  Every element of q is written. */
+int srmi_consistency_adjoint_gather(const float* g, int C, int h, int w, int scale, int umode, float* q,
+                                    void* stream);
+/* One step on LR-size buffers: Q = (first ? 0 : Q) + t, then t_out = M t - G^T (M t), at every
+ * cell (t_out is not masked; an inactive cell of t is read as an exact zero).  Along an axis
+ * G^T gathers from i = j - 2 .. j + 2 with w^T[j, i] = sum_o g_o [clamp(i + o) = j], g as in
+ * srmi_consistency_iterate.  Started from t = q with first = 1 and ping-ponged, K launches
+ * leave Q = sum_{k < K} t_k.  `active` is srmi_consistency_residual's.  t, Q and t_out must be
+ * three different buffers: SRMI_ERR_ARG otherwise. */
+int srmi_consistency_adjoint_iterate(const float* t, const int* active, int C, int h, int w, int scale, int umode,
+                                     int dmode, int first, float* Q, float* t_out, void* stream);
+/* g [C][h s][w s] -= D^T (M Q), in place: g[Y][X] -= k(Y mod s) k(X mod s) Q[Y / s][X / s] at
+ * the tap phases of D inside the blocks of the active cells.  Pixels at the other phases (at
+ * scale 8 under a bicubic D: 0, 1, 6, 7) and the blocks of inactive cells are neither read
+ * nor written.  16- or 8-byte accesses where the taps fill an aligned quad or pair (scale %
+ * 4 == 0, bicubic D, g 16-byte aligned). */
+int srmi_consistency_adjoint_apply(const float* Q, const int* active, int C, int h, int w, int scale, int dmode,
+                                   float* g, void* stream);
 
 /* ---- the spectral loss term (no reference counterpart) ------------------ */
 /* A Fourier-space term beside the pixel loss of a training step: the windowed amplitudes

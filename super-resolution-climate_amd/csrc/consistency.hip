@@ -21,6 +21,9 @@
 //                                neighbourhood of R once, combined along y first; then per
 //                                pixel the x weights of srmi_upsample / srmi_interpolate.
 //                                Finite pixels are updated, the others never written.
+// and the three of the correction's adjoint (training through it), described where they
+// stand: consistency_adjoint_gather_kernel (U^T, the one kernel here that uses LDS),
+// consistency_adjoint_iterate_kernel and consistency_adjoint_apply_kernel.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -232,6 +235,196 @@ __global__ void __launch_bounds__(kConsThreads)
   }
 }
 
+// ----------------------------------------------------------------------- adjoint
+// The correction is linear in x0: x_K = x0 + U P M (lr - D x0), P = sum_{k < K} E^k, E =
+// M (I - G), G the clamped D U stencil.  Its transpose applied to a gradient g is
+//     q = U^T g;  t_0 = q, t_{k+1} = (I - G^T)(M t_k), Q = sum_{k < K} t_k;  g0 = g - D^T (M Q)
+// -- the three kernels below, each a gather with a fixed summation order.
+
+// One axis of U^T as a table: row e holds, for HR index X0 + e (block c = X / s), the
+// weight of that pixel on the LR cells c - 2 .. c + 2, the clamped taps of cons_up_axis
+// folded onto the cell they read (ascending tap order).  Zero outside the field.
+__device__ __forceinline__ void cons_ut_table(float* tab, int count, int X0, int n, int s, int umode, float inv) {
+  const int nt = umode == 1 ? 2 : 4;
+  for (int e = threadIdx.x; e < count; e += blockDim.x) {
+    const int X = X0 + e;
+    float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (X >= 0 && X < n * s) {
+      float wt[4];
+      const int x0 = cons_up_axis(umode, inv, X, n, wt);
+      const int c = X / s;
+#pragma unroll
+      for (int o = 0; o < 5; ++o) {
+        float sum = 0.f;
+        for (int ti = 0; ti < nt; ++ti)
+          if (min(max(x0 + ti, 0), n - 1) == c + o - 2) sum += wt[ti];
+        o5[o] = sum;
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < 5; ++o) tab[e * 5 + o] = o5[o];
+  }
+}
+
+// q = U^T g.  One workgroup per (band of TB LR rows, strip of TX LR columns), looping over
+// its planes: the two axis tables once, then per plane the band's (TB + 4) s HR rows
+// reduced along x into LDS (each LR column from the 5 s pixels of its 5 neighbouring
+// blocks, ascending X) and those reduced along y (ascending Y).  The strip bounds the LDS
+// whatever w s is.  VEC: s % 4 == 0 and g 16-byte aligned -- a block's pixels as float4.
+template <bool VEC>
+__global__ void __launch_bounds__(kConsThreads)
+    consistency_adjoint_gather_kernel(const float* __restrict__ g, int NC, int h, int w, int s, int umode, int TB,
+                                      int TX, int nstrips, float* __restrict__ q) {
+  extern __shared__ float cons_lds[];
+  const int rows = (TB + 4) * s, cols = (TX + 4) * s;
+  float* tabx = cons_lds;           // [cols][5]
+  float* taby = tabx + cols * 5;    // [rows][5]
+  float* xbuf = taby + rows * 5;    // [rows][TX]
+  const int jy0 = (blockIdx.x / nstrips) * TB, jx0 = (blockIdx.x % nstrips) * TX;
+  const int nby = min(TB, h - jy0), nbx = min(TX, w - jx0);
+  const int Y0 = (jy0 - 2) * s, X0 = (jx0 - 2) * s;
+  const int H = h * s;
+  const size_t W = (size_t)w * s;
+  const int rad = umode == 1 ? 1 : 2;
+  const float inv = 1.f / (float)s;
+  cons_ut_table(tabx, cols, X0, w, s, umode, inv);
+  cons_ut_table(taby, rows, Y0, h, s, umode, inv);
+  __syncthreads();
+  for (size_t nc = blockIdx.y; nc < (size_t)NC; nc += gridDim.y) {
+    const float* src = g + nc * H * W;
+    for (int e = threadIdx.x; e < rows * nbx; e += blockDim.x) {
+      const int r = e / nbx, jl = e % nbx;
+      const int Y = Y0 + r, jx = jx0 + jl;
+      if (Y < 0 || Y >= H) continue;  // never read below
+      const float* row = src + (size_t)Y * W;
+      float acc = 0.f;
+      for (int c = max(jx - rad, 0); c <= min(jx + rad, w - 1); ++c) {
+        const float* tw = tabx + (c * s - X0) * 5 + (jx - c + 2);
+        if (VEC) {
+          const float4* p4 = reinterpret_cast<const float4*>(row + (size_t)c * s);
+          for (int k = 0; k < s / 4; ++k) {
+            const float4 f = p4[k];
+            acc += tw[(4 * k) * 5] * f.x;
+            acc += tw[(4 * k + 1) * 5] * f.y;
+            acc += tw[(4 * k + 2) * 5] * f.z;
+            acc += tw[(4 * k + 3) * 5] * f.w;
+          }
+        } else {
+          for (int p = 0; p < s; ++p) acc += tw[p * 5] * row[(size_t)c * s + p];
+        }
+      }
+      xbuf[r * TX + jl] = acc;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nby * nbx; e += blockDim.x) {
+      const int jyl = e / nbx, jl = e % nbx;
+      const int jy = jy0 + jyl;
+      float acc = 0.f;
+      for (int c = max(jy - rad, 0); c <= min(jy + rad, h - 1); ++c) {
+        const int r0 = c * s - Y0;
+        const int o = jy - c + 2;
+        for (int p = 0; p < s; ++p) acc += taby[(r0 + p) * 5 + o] * xbuf[(r0 + p) * TX + jl];
+      }
+      q[nc * h * w + (size_t)jy * w + jx0 + jl] = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// Q (+)= t, t_out = M t - G^T (M t): one thread per LR cell.  Along an axis of n cells the
+// transposed clamped stencil gathers from i = j - 2 .. j + 2 with w^T[j, i] = sum over o of
+// g_o [clamp(i + o) = j] (the edge taps folded, ascending o); x taps summed per row in
+// ascending i, rows then in ascending i.  An inactive cell is read as an exact zero.
+__global__ void __launch_bounds__(kConsThreads)
+    consistency_adjoint_iterate_kernel(const float* __restrict__ t, const int* __restrict__ active, int NC, int h,
+                                       int w, ConsStencil st, int first, float* __restrict__ Q,
+                                       float* __restrict__ t_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h * w) return;
+  const int x = i % w, y = i / w;
+  const int rad = st.radius;
+  float wy[5], wx[5];
+#pragma unroll
+  for (int d = 0; d < 5; ++d) {
+    float sy = 0.f, sx = 0.f;
+    const int iy = y + d - 2, ix = x + d - 2;
+    for (int o = -rad; o <= rad; ++o) {
+      if (iy >= 0 && iy < h && min(max(iy + o, 0), h - 1) == y) sy += st.gy[o + 2];
+      if (ix >= 0 && ix < w && min(max(ix + o, 0), w - 1) == x) sx += st.gy[o + 2];
+    }
+    wy[d] = sy;
+    wx[d] = sx;
+  }
+  for (size_t nc = blockIdx.y; nc < (size_t)NC; nc += gridDim.y) {
+    const float* src = t + nc * h * w;
+    const int* act = active + nc * h * w;
+    const size_t o = nc * h * w + i;
+    const float c = src[i];
+    Q[o] = first ? c : Q[o] + c;
+    float acc = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 5; ++dy) {
+      const int yy = y + dy - 2;
+      if (dy < 2 - rad || dy > 2 + rad || yy < 0 || yy >= h) continue;
+      float rsum = 0.f;
+#pragma unroll
+      for (int dx = 0; dx < 5; ++dx) {
+        const int xx = x + dx - 2;
+        if (dx < 2 - rad || dx > 2 + rad || xx < 0 || xx >= w) continue;
+        const int idx = yy * w + xx;
+        rsum += wx[dx] * (act[idx] ? src[idx] : 0.f);
+      }
+      acc += wy[dy] * rsum;
+    }
+    t_out[o] = (act[i] ? c : 0.f) - acc;
+  }
+}
+
+// g -= D^T (M Q): one thread per (tap row of D, LR cell) -- the NT tap pixels of that row
+// inside the cell's block, g[Y, X] -= (k(Y mod s) k(X mod s)) Q[cell]; the products of two
+// taps are exact in fp32.  Rows and pixels at non-tap phases, and the blocks of inactive
+// cells, are never touched.  VEC (s % 4 == 0, g 16-byte aligned): taps that fill an
+// aligned quad (bicubic at s = 4) go as one float4, an aligned pair as one float2.
+template <bool VEC, int NT>
+__global__ void __launch_bounds__(kConsThreads)
+    consistency_adjoint_apply_kernel(const float* __restrict__ Q, const int* __restrict__ active, int NC, int h, int w,
+                                     int s, float* __restrict__ g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h * NT * w) return;
+  const int d = i % w, tr = i / w;
+  const int y = tr / NT, ti = tr % NT;
+  const int a = s / 2 - NT / 2;
+  const size_t W = (size_t)w * s, H = (size_t)h * s;
+  float k[4];
+  if (NT == 4) {
+    k[0] = -3.f / 32.f, k[1] = 19.f / 32.f, k[2] = 19.f / 32.f, k[3] = -3.f / 32.f;
+  } else {
+    k[0] = 0.5f, k[1] = 0.5f, k[2] = 0.f, k[3] = 0.f;
+  }
+  const float ky = k[ti];
+  for (size_t nc = blockIdx.y; nc < (size_t)NC; nc += gridDim.y) {
+    const size_t o = nc * h * w + (size_t)y * w + d;
+    if (!active[o]) continue;
+    const float v = Q[o];
+    float* dst = g + nc * H * W + ((size_t)y * s + a + ti) * W + (size_t)d * s + a;
+    if (VEC && NT == 4 && (a & 3) == 0) {
+      float4 f = *reinterpret_cast<float4*>(dst);
+      f.x -= (ky * k[0]) * v, f.y -= (ky * k[1]) * v, f.z -= (ky * k[2]) * v, f.w -= (ky * k[3]) * v;
+      *reinterpret_cast<float4*>(dst) = f;
+    } else if (VEC && (a & 1) == 0) {
+#pragma unroll
+      for (int p = 0; p < NT / 2; ++p) {
+        float2 f = reinterpret_cast<float2*>(dst)[p];
+        f.x -= (ky * k[2 * p]) * v, f.y -= (ky * k[2 * p + 1]) * v;
+        reinterpret_cast<float2*>(dst)[p] = f;
+      }
+    } else {
+#pragma unroll
+      for (int tj = 0; tj < NT; ++tj) dst[tj] -= (ky * k[tj]) * v;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------- host
 double cons_cubic1(double x) { return ((1.25 * x - 2.25) * x) * x + 1.0; }                     // |x| <= 1, A = -0.75
 double cons_cubic2(double x) { return ((-0.75 * x + 3.75) * x - 6.0) * x + 3.0; }               // 1 < |x| < 2
@@ -247,6 +440,14 @@ int cons_shape(int C, int h, int w, int s, int* gy) {
   if ((long long)h * s * w * s >= (1ll << 31)) return SRMI_ERR_SHAPE;
   *gy = C < kConsMaxGridY ? C : kConsMaxGridY;
   return 0;
+}
+
+// LDS of the adjoint gather at a band of tb LR rows and a strip of tx LR columns: the two
+// axis tables and the x-reduced rows.  14.3 KB at tb = 8, tx = 48, s = 4.
+constexpr size_t kConsGatherLds = 48 * 1024;
+size_t cons_gather_lds(int tb, int tx, int s) {
+  const size_t rows = (size_t)(tb + 4) * s, cols = (size_t)(tx + 4) * s;
+  return sizeof(float) * (5 * cols + 5 * rows + rows * tx);
 }
 
 // D U along one axis, in double from ATen's weights: g[o + 2] = sum over the taps j of D
@@ -339,6 +540,81 @@ int srmi_consistency_apply(const float* R, int C, int h, int w, int scale, int u
     hipLaunchKernelGGL(consistency_apply_kernel<true>, grid, block, 0, st, R, C, h, w, scale, umode, hr);
   else
     hipLaunchKernelGGL(consistency_apply_kernel<false>, grid, block, 0, st, R, C, h, w, scale, umode, hr);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_consistency_adjoint_gather(const float* g, int C, int h, int w, int scale, int umode, float* q,
+                                    void* stream) {
+  if (!g || !q || !cons_mode_ok(umode)) return SRMI_ERR_ARG;
+  if (!cons_scale_ok(scale, SRMI_INTERP_BILINEAR)) return SRMI_ERR_SHAPE;
+  int gy;
+  const int rc = cons_shape(C, h, w, scale, &gy);
+  if (rc) return rc;
+  // the band / strip: the largest that fits kConsGatherLds, columns first (a strip of 8
+  // columns and a band of one row need 31.6 KB at scale 64, so one always fits); then
+  // smaller bands while the grid would leave most of the chip idle
+  int TB = 1, TX = w < 8 ? w : 8;
+  bool found = false;
+  const int txs[4] = {64, 32, 16, 8}, tbs[4] = {8, 4, 2, 1};
+  for (int b = 0; b < 4 && !found; ++b)
+    for (int a = 0; a < 4 && !found; ++a) {
+      const int tb = tbs[b] < h ? tbs[b] : h, tx = txs[a] < w ? txs[a] : w;
+      if (cons_gather_lds(tb, tx, scale) <= kConsGatherLds) TB = tb, TX = tx, found = true;
+    }
+  const int nstrips = (w + TX - 1) / TX;
+  while (TB > 1 && (long long)gy * ((h + TB - 1) / TB) * nstrips < 256) TB = (TB + 1) / 2;
+  const dim3 grid(((h + TB - 1) / TB) * nstrips, gy), block(kConsThreads);
+  const size_t lds = cons_gather_lds(TB, TX, scale);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (scale % 4 == 0 && ((uintptr_t)g & 15) == 0)
+    hipLaunchKernelGGL(consistency_adjoint_gather_kernel<true>, grid, block, lds, st, g, C, h, w, scale, umode, TB, TX,
+                       nstrips, q);
+  else
+    hipLaunchKernelGGL(consistency_adjoint_gather_kernel<false>, grid, block, lds, st, g, C, h, w, scale, umode, TB,
+                       TX, nstrips, q);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_consistency_adjoint_iterate(const float* t, const int* active, int C, int h, int w, int scale, int umode,
+                                     int dmode, int first, float* Q, float* t_out, void* stream) {
+  if (!t || !active || !Q || !t_out || t == t_out || t == Q || Q == t_out || !cons_mode_ok(umode) ||
+      !cons_mode_ok(dmode))
+    return SRMI_ERR_ARG;
+  if (!cons_scale_ok(scale, dmode)) return SRMI_ERR_SHAPE;
+  int gy;
+  const int rc = cons_shape(C, h, w, scale, &gy);
+  if (rc) return rc;
+  ConsStencil stc;
+  cons_stencil(scale, umode, dmode, &stc);
+  hipLaunchKernelGGL(consistency_adjoint_iterate_kernel, dim3((h * w + kConsThreads - 1) / kConsThreads, gy),
+                     dim3(kConsThreads), 0, static_cast<hipStream_t>(stream), t, active, C, h, w, stc, first ? 1 : 0,
+                     Q, t_out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_consistency_adjoint_apply(const float* Q, const int* active, int C, int h, int w, int scale, int dmode,
+                                   float* g, void* stream) {
+  if (!Q || !active || !g || !cons_mode_ok(dmode)) return SRMI_ERR_ARG;
+  if (!cons_scale_ok(scale, dmode)) return SRMI_ERR_SHAPE;
+  int gy;
+  const int rc = cons_shape(C, h, w, scale, &gy);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool cubic = dmode == SRMI_INTERP_BICUBIC;
+  const long long cells = (long long)h * (cubic ? 4 : 2) * w;  // < 2^31: at most the plane's pixels
+  const dim3 grid((unsigned)((cells + kConsThreads - 1) / kConsThreads), gy), block(kConsThreads);
+  const bool vec = scale % 4 == 0 && ((uintptr_t)g & 15) == 0;
+#define SRMI_CONS_ADJ(VV, NT) \
+  hipLaunchKernelGGL((consistency_adjoint_apply_kernel<VV, NT>), grid, block, 0, st, Q, active, C, h, w, scale, g)
+  if (vec) {
+    if (cubic) SRMI_CONS_ADJ(true, 4); else SRMI_CONS_ADJ(true, 2);
+  } else {
+    if (cubic) SRMI_CONS_ADJ(false, 4); else SRMI_CONS_ADJ(false, 2);
+  }
+#undef SRMI_CONS_ADJ
   SRMI_CHECK_LAUNCH();
   return 0;
 }

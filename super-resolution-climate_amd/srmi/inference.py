@@ -33,7 +33,9 @@ import torch
 
 from ._lib import SRMI_LOSS_MEAN, SRMI_LOSS_RMSE, call, ptr, stream_handle
 from .dist import DistInfo
+from .consistency import ConsistencyLayer
 from .engine import Engine, NetSpec, downsample, engine_stream, interp_size, upsample
+from .superres import check_consistent
 
 LOSS_KINDS = {"l2": SRMI_LOSS_RMSE, "charbonnier": SRMI_LOSS_MEAN}
 CHARBONNIER_EPS = 1e-6  # dual_trainer.py:122
@@ -64,7 +66,8 @@ class TiledInference:
     def __init__(self, spec: NetSpec, params: torch.Tensor, region_chw: Tuple[int, int, int],
                  tile_hr: Tuple[int, int] = (192, 192), device: Optional[torch.device] = None, graph: bool = True,
                  micro: Optional[int] = None, batch_size: int = 36, loss_fn: str = "l2",
-                 info: Optional[DistInfo] = None, task=None, norm: Optional[str] = None, stats=None):
+                 info: Optional[DistInfo] = None, task=None, norm: Optional[str] = None, stats=None,
+                 consistent: int = 0):
         """batch_size: task.batch_size (the tiles scored per batch; 36 in every
         reference task yaml); loss_fn: model.loss_fn.
 
@@ -83,7 +86,16 @@ class TiledInference:
         holds the full mosaics and the per-batch losses, bit-identical to one rank:
         the forward is batch-invariant (every tile is computed alone, whatever engine
         batch it rides in) and the batch losses are formed from the gathered per-tile
-        sums in the one-rank order (srmi_batch_loss_means).  No graph in this mode."""
+        sums in the one-rank order (srmi_batch_loss_means).  No graph in this mode.
+
+        consistent (no reference counterpart; DESIGN.md §1 "Consistency in training"): K in
+        0 .. 16, the K a model was trained with under FusedTrainer(consistent=K).  K > 0
+        runs the same parameter-free last layer (srmi.consistency.ConsistencyLayer) on every
+        tile's output against that tile's LR input, in normalised units, right after the
+        engines and before the losses and the mosaics, in every path (plain, graph,
+        compacted, multi-rank): 'model' and its loss are the constrained model's.  An odd
+        scale, a scale below 4 under a bicubic downsample, or a mode other than bilinear /
+        bicubic raises ValueError.  consistent=0 is the object as it was."""
         if loss_fn not in LOSS_KINDS:
             raise ValueError(f"Unknown single-product loss function {loss_fn}")
         if task is None:  # the active srmi ConfigContext's task section, if any
@@ -101,6 +113,7 @@ class TiledInference:
         self.ds = data_downsample_factor(task)
         # task.downsample_mode / upsample_mode (torch_interp_mode, array.py:37-41)
         self.dmode, self.umode = interp_mode(task, True), interp_mode(task, False)
+        self.consistent = check_consistent(consistent, spec.scale, self.dmode, self.umode)
         self.loss_kind = LOSS_KINDS[loss_fn]
         self.batch_size = int(batch_size)
         self.spec = spec
@@ -149,6 +162,8 @@ class TiledInference:
         self.lr = torch.empty((n, C, ty // s, tx // s), **f32)
         self.sr = torch.empty((n, C, ty, tx), **f32)
         self.interp = torch.empty((n, C, ty, tx), **f32)
+        self.layer = (ConsistencyLayer((n, C, ty // s, tx // s), s, self.umode, self.dmode, self.consistent, d)
+                      if self.consistent else None)
         nb = (n + self.batch_size - 1) // self.batch_size
         self.loss_m = torch.zeros(1 + nb, **f32)   # [mean of batch losses, batch losses...]
         self.loss_i = torch.zeros(1 + nb, **f32)
@@ -228,6 +243,8 @@ class TiledInference:
         for sk, ev in zip(self.streams[1:], self.ev_join):
             ev.record(sk)
             main.wait_event(ev)
+        if self.layer is not None:  # the model's last layer: sr corrected in place, per tile
+            self.layer.forward_(sr[:nt], lr[:nt])
         upsample(lr, self.s, out=interp, mode=self.umode)
         te = self.C * self.ty * self.tx
         for pred, lo in ((sr, self.loss_m), (interp, self.loss_i)):
@@ -398,6 +415,8 @@ class TiledInference:
                 if b > a:
                     e.forward(self.params, self.sub_lr[a:b], out=self.sub_sr[a:b])
                 a = b
+            if self.layer is not None:
+                self.layer.forward_(self.sub_sr[:nl], self.sub_lr[:nl])
             upsample(self.sub_lr[:nl], self.s, out=self.sub_interp[:nl], mode=self.umode)
         st = stream_handle()
         te = self.C * self.ty * self.tx

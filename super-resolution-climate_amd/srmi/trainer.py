@@ -28,7 +28,9 @@ from ._lib import SRMI_LOSS_MEAN, SRMI_LOSS_RMSE, TILE_LOSS_SUB, call, ptr
 from .config import check_fused_task, data_downsample_factor, interp_mode
 from .dist import DistInfo, GradReducer, allreduce_sum_
 from .engine import Engine, NetSpec, adam_step, axpy, downsample, engine_stream, interp_size, upsample
+from .consistency import ConsistencyLayer
 from .spectra import SpectralLoss, check_spectral_loss_config
+from .superres import check_consistent
 
 LOSS_KINDS = {"l2": SRMI_LOSS_RMSE, "charbonnier": SRMI_LOSS_MEAN}
 CHARBONNIER_EPS = 1e-6  # ModelTrainer.eps, sres/controller/dual_trainer.py:122
@@ -72,7 +74,7 @@ class FusedTrainer:
                  info: Optional[DistInfo] = None, device: Optional[torch.device] = None, seed: int = 0,
                  params: Optional[torch.Tensor] = None, micro: Optional[int] = None, loss_fn: str = "l2",
                  cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
-                 land: bool = False, spectral: Optional[Mapping] = None):
+                 land: bool = False, spectral: Optional[Mapping] = None, consistent: int = 0):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -101,12 +103,30 @@ class FusedTrainer:
         Fourier amplitudes of sr - target over the global batch, and the backward runs from
         the sum of both upstream gradients.  Windows that touch a non-finite pixel are
         skipped, so land=True needs nothing more.  A bad window, stride, weight (finite,
-        >= 0) or eps raises ValueError here."""
+        >= 0) or eps raises ValueError here.
+        consistent (no reference counterpart; DESIGN.md §1 "Consistency in training"): K in
+        0 .. 16.  K > 0 makes K steps of back-projection onto the LR input the model's last,
+        parameter-free layer (srmi.consistency.ConsistencyLayer): the network's output is
+        corrected in place right after the forward, so the pixel loss, the spectral term and
+        ``sr`` see the corrected field, and the upstream gradient goes through the layer's
+        adjoint before the engine's backward.  The constraint is imposed against the LR batch
+        as downsampled; land=True: as it was BEFORE the flood fill, so a cell whose coarse
+        value is NaN is left unconstrained.  It needs nchannels_out == nchannels_in without
+        a task.target_variables selection, an even scale (>= 4 under a bicubic downsample)
+        and bilinear / bicubic modes: ValueError otherwise, before anything is allocated.
+        K is no parameter and is not stored in a checkpoint: pass the same K to
+        TiledInference / RegionSuperResolver.  consistent=0 is the trainer as it was."""
         if loss_fn not in LOSS_KINDS:  # single_product_loss, dual_trainer.py:210-211
             raise ValueError(f"Unknown single-product loss function {loss_fn}")
         if task is None:
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
+        # consistent > 0 (the integer alone is checked here, scale and modes below): the layer
+        # compares the output with the input channel by channel, so a target_variables subset
+        # (fewer output channels) has no meaning -- said before check_fused_task looks for names
+        if check_consistent(consistent, 2, "bilinear", "bilinear") and spec.nchannels_out != spec.nchannels_in:
+            raise ValueError(f"consistent={consistent} needs a model whose output channels are its input's (no "
+                             f"task.target_variables subset): {spec.nchannels_in} in, {spec.nchannels_out} out")
         tindx = check_fused_task(task, spec.nchannels_in, spec.nchannels_out)
         self.ds = data_downsample_factor(task)
         self.land = bool(land)
@@ -114,6 +134,7 @@ class FusedTrainer:
             raise ValueError(f"land=True with task.data_downsample={self.ds}: the land mask of a pre-downsampled "
                              "HR batch is not defined (train on tiles of the model's own HR size)")
         self.dmode, self.umode = interp_mode(task, True), interp_mode(task, False)
+        self.consistent = check_consistent(consistent, spec.scale, self.dmode, self.umode)
         if tindx is not None and interp_loss and spec.nchannels_out != 1:
             # loss(btarget, upsample(binput)) (:315-317) needs equal or broadcastable channels
             raise ValueError(f"interp loss of a {spec.nchannels_out}-channel target against the "
@@ -173,8 +194,14 @@ class FusedTrainer:
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
         # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
         # (a spectral term: always -- its gradient is added to the pixel loss's)
+        # (a consistency layer: always -- its adjoint runs on it)
         self.dy = (torch.empty_like(self.sr)
-                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None else None)
+                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None or self.consistent
+                   else None)
+        # the consistency layer and, with land, the LR batch as it was before the flood fill
+        self.layer = (ConsistencyLayer((batch, C, h, w), s, self.umode, self.dmode, self.consistent, self.device)
+                      if self.consistent else None)
+        self.lr_raw = torch.empty_like(self.lrbuf) if self.consistent and self.land else None
         # the selected target channels (index_select) and, for the interp metric, that
         # target broadcast over the input's channels (1-channel target, :316-317)
         self.tgt = torch.empty_like(self.sr) if self.tindx is not None else None
@@ -327,9 +354,14 @@ class FusedTrainer:
                 downsample(hr[sl], s, out=self.lrbuf[sl], mode=self.dmode)
                 if self.land:  # an LR pixel is NaN iff one of its taps is dry: fill, as inference does
                     lrs = self.lrbuf[sl]
+                    if self.lr_raw is not None:
+                        self.lr_raw[sl].copy_(lrs)
                     call("srmi_tiles_fill", ptr(lrs), lrs.shape[0] * lrs.shape[1], lrs.shape[2], lrs.shape[3], None,
                          torch.cuda.current_stream(self.device).cuda_stream)
                 eng.forward(self.params, self.lrbuf[sl], out=self.sr[sl])
+                if self.layer is not None:  # the last layer: sr corrected in place
+                    self.layer.forward_(self.sr[sl], (self.lrbuf if self.lr_raw is None else self.lr_raw)[sl],
+                                        rows=sl.start)
                 if self.dy is not None and not self.land:  # Charbonnier: the elementwise upstream gradient only
                     eng.charbonnier_partial(self.sr[sl], tgt[sl], None, count, CHARBONNIER_EPS, dy=self.dy[sl])
                 self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start, lcparts)
@@ -349,8 +381,10 @@ class FusedTrainer:
         for st in self.streams[1:]:
             st.wait_stream(main)
         # the upstream gradient from the finalised loss, zero on land; with a spectral term
-        # the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then the term's on top
-        if self.land or (self.spectral is not None and self.loss_kind == SRMI_LOSS_RMSE):
+        # or a consistency layer the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then
+        # the term's on top
+        explicit = self.spectral is not None or self.layer is not None
+        if self.land or (explicit and self.loss_kind == SRMI_LOSS_RMSE):
             for k in range(self.micro):
                 sl = sls[k]
                 if sl.stop > sl.start:
@@ -364,6 +398,12 @@ class FusedTrainer:
                 if sl.stop > sl.start:
                     with self._ctx(k):
                         self.spectral.add_dy(self.dy[sl], rows=sl.start)
+        if self.layer is not None:  # through the layer's adjoint: dy becomes the network output's gradient
+            for k in range(self.micro):
+                sl = sls[k]
+                if sl.stop > sl.start:
+                    with self._ctx(k):
+                        self.layer.backward_(self.dy[sl], rows=sl.start)
         # backward per micro-batch with the global loss scale.  Data parallel: the
         # engines' gradients are added and all-reduced bucket by bucket as soon as every
         # engine is past the bucket, overlapped with the rest of backward
