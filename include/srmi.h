@@ -240,6 +240,24 @@ int srmi_engine_probe(srmi_engine* e, int which, int reps, void* stream);
  * Both persist after a forward, in inference engines too. */
 #define SRMI_BUF_RESB 10
 #define SRMI_BUF_PS 11
+/* The backward's maps outside the residual groups (train engines; else SRMI_ERR_ARG), read-only
+ * views for the per-launch tests:
+ *   DPS(g = k): the gradient w.r.t. PS(k), operand type, shaped as PS(k); DPS(nups - 1) is the
+ *     tail conv's dgrad, DPS(k - 1) upsampler k's.  Valid after backward stage 0 until the next
+ *     backward.
+ *   DRESB: the operand-type copy of DRESF (upsampler 0's dgrad writes both), same validity.
+ *   BODY_GRAD(b = 0 fp32 | b = 1 operand type): the gradient w.r.t. the body's last block
+ *     output, as the body tail's dgrad leaves it.  RCAN: valid after stage 0 until stage 1 runs
+ *     (the groups' stages alternate this buffer with a second one).  EDSR's one-stage backward
+ *     reuses it for every second ResBlock: it is that gradient at nlayers == 1 only.
+ *   HEAD_GRAD: the fp32 gradient w.r.t. the head's output, what the head's filter gradient
+ *     reads.  RCAN: the same buffer as GROUP_IN_GRAD(0), valid after stage nlayers; EDSR: after
+ *     the backward.
+ * b outside 0 .. 1 (BODY_GRAD), g outside 0 .. log2(scale) - 1 (DPS): SRMI_ERR_ARG. */
+#define SRMI_BUF_DPS 12
+#define SRMI_BUF_DRESB 13
+#define SRMI_BUF_BODY_GRAD 14
+#define SRMI_BUF_HEAD_GRAD 15
 int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size_t* elems, int* elem_bytes);
 
 /* diagnostic (tests): trace of the RCAN backward's in-group state, which every RCAB of a

@@ -1263,6 +1263,25 @@ int srmi_engine_buffer(srmi_engine* e, int which, int g, int b, void** ptr, size
       p = e->PS[g];
       n = e->mapn << (2 * (g + 1));
       break;
+    case SRMI_BUF_DPS:
+      if (!e->train || g < 0 || g >= e->P.nups) return SRMI_ERR_ARG;
+      p = e->dPS[g];
+      n = e->mapn << (2 * (g + 1));
+      break;
+    case SRMI_BUF_DRESB:
+      if (!e->train) return SRMI_ERR_ARG;
+      p = e->dRESb;
+      break;
+    case SRMI_BUF_BODY_GRAD:  // backward_impl's gRf / gRb as the body tail's dgrad writes them
+      if (!e->train || b < 0 || b > 1) return SRMI_ERR_ARG;
+      p = b ? static_cast<void*>(e->GAb) : e->GAf;
+      if (!b) eb = 4;
+      break;
+    case SRMI_BUF_HEAD_GRAD:  // backward_impl's gRf at the head (after nlayers swaps, RCAN and EDSR alike)
+      if (!e->train) return SRMI_ERR_ARG;
+      p = (nl & 1) ? e->GBf : e->GAf;
+      eb = 4;
+      break;
     default:
       return SRMI_ERR_ARG;
   }

@@ -30,7 +30,7 @@ SRMI_NORM_LSCALE = 1
 SRMI_NORM_AFFINE = 2
 # srmi_engine_buffer's `which` (SRMI_BUF_*)
 BUFFERS = {"X0F": 0, "HB": 1, "T": 2, "U": 3, "REC": 4, "BREC": 5, "DU": 6, "DZ": 7, "DRESF": 8, "GROUP_IN_GRAD": 9,
-           "RESB": 10, "PS": 11}
+           "RESB": 10, "PS": 11, "DPS": 12, "DRESB": 13, "BODY_GRAD": 14, "HEAD_GRAD": 15}
 # srmi_engine_trace_slot's `which` (SRMI_TRACE_*)
 TRACE_SLOTS = {"GRB": 0, "STREAM": 1, "PACC": 2, "DZ": 3, "DU": 4}
 # srmi_engine_fwd_trace_slot's `which` (SRMI_FTRACE_*)

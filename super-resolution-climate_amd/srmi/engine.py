@@ -149,7 +149,8 @@ class Engine:
         (no copy; srmi_engine_buffer), valid until the next forward / backward.  name:
         a key of _lib.BUFFERS.  Maps come as [n, h, w, 64] (n = the last forward's tiles)
         in the map's own type, the CA records REC / BREC as [n, 160] / [n, 224] fp32, the
-        upsamplers' outputs PS (g = k) as [n, h 2^(k+1), w 2^(k+1), 64]."""
+        upsamplers' outputs PS (g = k) and their gradients DPS as [n, h 2^(k+1), w 2^(k+1), 64].
+        BODY_GRAD: b = 0 the fp32 map, b = 1 its operand-type copy (srmi.h: when each is valid)."""
         if name not in _lib.BUFFERS:
             raise _lib.SrmiError(f"unknown engine buffer {name!r} ({' | '.join(_lib.BUFFERS)})")
         p, elems, eb = C.c_void_p(), C.c_size_t(), C.c_int()
@@ -162,7 +163,7 @@ class Engine:
         flat = self.workspace[off:off + nbytes].view(torch.float32 if eb.value == 4 else torch.bfloat16)
         n = getattr(self, "_last_n", self.batch)
         per = int(elems.value) // self.batch
-        if name == "PS":
+        if name in ("PS", "DPS"):
             return flat.view(self.batch, self.lr_h << (g + 1), self.lr_w << (g + 1), 64)[:n]
         return flat.view(self.batch, *((self.lr_h, self.lr_w, 64) if name not in ("REC", "BREC") else (per,)))[:n]
 
