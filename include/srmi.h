@@ -23,6 +23,13 @@
  *   srmi_downsample/_upsample    -> sres/base/util/array.py:72-76 / :84-87
  *   srmi_interpolate             -> the same with torch_interp_mode, array.py:37-41
  *   srmi_adam_step               -> torch.optim.Adam, dual_trainer.py:126,323
+ *   srmi_grad_norm_workspace,
+ *   srmi_grad_norm               -> torch.nn.utils.clip_grad_norm_ (norm, coefficient) and
+ *                                   a finite-norm flag.  The reference never clips.
+ *   srmi_adam_step_guarded       -> torch.optim.Adam on the clipped gradient, skipped when
+ *                                   the norm is not finite, and in the same pass
+ *                                   torch.optim.swa_utils.get_ema_multi_avg_fn's update of
+ *                                   averaged weights.  The reference keeps no average.
  *   srmi_conv3x3* / srmi_wgrad*  -> nn.Conv2d of default_conv
  *                                   sres/model/common/cnn.py:8-9 (op level)
  *   srmi_ca_*                    -> CALayer sres/model/rcan/network.py:31-47
@@ -379,6 +386,35 @@ int srmi_interpolate(const float* x, int N, int C, int H, int W, int Ho, int Wo,
 /* Adam on flat buffers, step counted from 1 */
 int srmi_adam_step(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
                    float beta2, float eps, float weight_decay, void* stream);
+
+/* ---- optimizer guards ("Optimizer guards") ----
+ * The control record ctl[4] (fp32, device; the caller zeroes it once) joins the two:
+ *   ctl[0]  the L2 norm of the flat gradient
+ *   ctl[1]  the clip coefficient min(1, max_norm / (norm + 1e-6)): clip_grad_norm_'s
+ *           formula, evaluated in fp64 and rounded; 0 when ctl[2] is 0
+ *   ctl[2]  1.0 if ctl[0] is finite, else 0.0
+ *   ctl[3]  the running count of calls that found it non-finite (a whole number held in
+ *           fp32, as the masked loss counts are): read, incremented, written back
+ * srmi_grad_norm: every square and every sum in fp64 (the product of two fp32 values is
+ * exact there): one partial per block into the workspace (srmi_grad_norm_workspace bytes,
+ * 8-byte aligned), added in index order by a second, single-workgroup launch.  No atomics;
+ * the number of partials depends on n alone; the same g gives the same bits on every run.
+ * A NaN or an infinity anywhere in g gives ctl[2] = 0.  max_norm = +inf: measure and
+ * guard, never clip (ctl[1] is exactly 1).  max_norm <= 0 or NaN, n < 1, a missing
+ * buffer or a workspace that is too small: SRMI_ERR_ARG, and nothing is launched. */
+int srmi_grad_norm_workspace(size_t n, size_t* bytes);
+int srmi_grad_norm(const float* g, size_t n, float max_norm, void* workspace, size_t ws_bytes, float* ctl,
+                   void* stream);
+/* srmi_adam_step on g' = fl(g * ctl[1]), the coefficient read from the device (the host
+ * never sees it): the same kernel body, so ctl[1] = 1 and ema = NULL give srmi_adam_step's
+ * bits.  ctl[2] == 0: the launch writes nothing, and p, m, v, ema stay bit for bit as they
+ * were.  The caller still counts the step: the bias corrections of the next one are those
+ * of step + 1, which keeps the host free of any read of ctl.  ema != NULL: the same pass
+ * does ema += (1 - ema_decay) * (p_new - ema), ema_decay in [0, 1) (SRMI_ERR_ARG otherwise)
+ * (torch.optim.swa_utils.get_ema_multi_avg_fn: ema.lerp_(p, 1 - decay)). */
+int srmi_adam_step_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, int step, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* ctl,
+                           void* stream);
 
 /* y += a * x (flat fp32; sums micro-batch gradients) */
 int srmi_axpy(float* y, const float* x, float a, size_t n, void* stream);

@@ -1423,6 +1423,33 @@ int srmi_adam_step(float* p, const float* g, float* m, float* v, size_t n, int s
   return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, S_(stream));
 }
 
+int srmi_grad_norm_workspace(size_t n, size_t* bytes) {
+  if (!bytes || n < 1) return SRMI_ERR_ARG;
+  *bytes = grad_norm_blocks(n) * sizeof(double);
+  return 0;
+}
+
+int srmi_grad_norm(const float* g, size_t n, float max_norm, void* workspace, size_t ws_bytes, float* ctl,
+                   void* stream) {
+  if (!g || !workspace || !ctl || n < 1 || !(max_norm > 0.f)) return SRMI_ERR_ARG;  // (a NaN max_norm too)
+  if (ws_bytes < grad_norm_blocks(n) * sizeof(double) || ((size_t)workspace & 7) || ((size_t)g & 3))
+    return SRMI_ERR_ARG;
+  return grad_norm_launch(g, n, max_norm, (double*)workspace, ctl, S_(stream));
+}
+
+int srmi_adam_step_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, int step, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* ctl,
+                           void* stream) {
+  if (step < 1 || !ctl) return SRMI_ERR_ARG;
+  if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return SRMI_ERR_ARG;
+  const double bc1 = 1.0 - std::pow((double)beta1, step);
+  const double bc2 = 1.0 - std::pow((double)beta2, step);
+  const float step_size = (float)(lr / bc1);
+  const float bc2_sqrt = (float)std::sqrt(bc2);
+  return adam_guarded_launch(p, g, m, v, ema, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, ema_decay, ctl,
+                             S_(stream));
+}
+
 // ---------------------------------------------------------------- op level
 int srmi_conv3x3(const void* x, const void* wpack, const float* bias, int N, int H, int W, int Cin, int Cout,
                  int in_unshuffle, int epi, void* yb, float* yf, const float* r1, const float* r2, const float* r3,

@@ -1718,19 +1718,143 @@ int ca_param_grads_batched_launch(const float* recs, const float* brecs, int nbl
 // ============================================================================ Adam
 // torch.optim.Adam (foreach path): m.lerp_(g, 1-b1); v = b2 v + (1-b2) g^2;
 // p -= step_size * m / (sqrt(v)/sqrt(bc2) + eps)
+// One element body, two kernels.  GUARD: the step of srmi_adam_step_guarded -- nothing is written when
+// ctl[2] == 0 (a non-finite gradient norm), and g is scaled by the clip coefficient ctl[1],
+// the product rounded to fp32 on its own (never contracted into the operations that use it),
+// so the step is adam_kernel's on g' = fl(g ctl[1]) and, at ctl[1] = 1, adam_kernel's bits.
+// EMA: ema += (1 - ema_decay) (p' - ema) from the p' still in registers
+// (torch.optim.swa_utils.get_ema_multi_avg_fn: ema.lerp_(p, 1 - decay)).
+template <bool GUARD, bool EMA>
+__device__ __forceinline__ void adam_elem(size_t i, float* __restrict__ p, const float* __restrict__ g,
+                                          float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
+                                          float b1, float b2, float eps, float wd, float step_size, float bc2_sqrt,
+                                          float ema_decay, float coef) {
+  float gi = g[i];
+  // g' = fl(g coef) as an instruction of its own: the compiler can neither contract the product
+  // into the operations below nor pair it with wd * p, so they compile as adam_kernel's do
+  if (GUARD) asm("v_mul_f32 %0, %1, %2" : "=v"(gi) : "v"(gi), "v"(coef));
+  const float pi = p[i];
+  if (wd != 0.f) gi += wd * pi;
+  const float mi = m[i] + (1.f - b1) * (gi - m[i]);
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  const float pn = pi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+  p[i] = pn;
+  if (EMA) {
+    const float ei = ema[i];
+    ema[i] = ei + (1.f - ema_decay) * (pn - ei);
+  }
+}
+
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, size_t n, float b1, float b2, float eps, float wd,
                             float step_size, float bc2_sqrt) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    const float pi = p[i];
-    if (wd != 0.f) gi += wd * pi;
-    const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    adam_elem<false, false>(i, p, g, m, v, nullptr, b1, b2, eps, wd, step_size, bc2_sqrt, 0.f, 1.f);
+}
+
+template <bool EMA>
+__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, float* __restrict__ ema, size_t n, float b1, float b2,
+                                    float eps, float wd, float step_size, float bc2_sqrt, float ema_decay,
+                                    const float* __restrict__ ctl) {
+  if (ctl[2] == 0.f) return;  // a non-finite norm: the whole launch writes nothing
+  const float coef = ctl[1];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    adam_elem<true, EMA>(i, p, g, m, v, ema, b1, b2, eps, wd, step_size, bc2_sqrt, ema_decay, coef);
+}
+
+int adam_guarded_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, float b1, float b2,
+                        float eps, float wd, float step_size, float bc2_sqrt, float ema_decay, const float* ctl,
+                        hipStream_t st) {
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (ema)
+    hipLaunchKernelGGL(adam_guarded_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
+                       step_size, bc2_sqrt, ema_decay, ctl);
+  else
+    hipLaunchKernelGGL(adam_guarded_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
+                       step_size, bc2_sqrt, ema_decay, ctl);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ gradient norm
+// torch.nn.utils.clip_grad_norm_ on the flat gradient: the L2 norm, the clip coefficient
+// min(1, max_norm / (norm + 1e-6)) and whether the norm is finite, into ctl[4] on the device.
+// The squares and their sums are fp64 (the product of two fp32 values is exact in fp64, and
+// 3.4e38^2 * 2^32 is far from its range, so only a non-finite element makes the sum
+// non-finite).  Every block writes one partial (fixed tree), grad_norm_finalize_kernel adds
+// them in index order: no atomics, the partial count a function of n alone, the same bits
+// on every run (tile_loss_parts / loss_from_parts' convention).  A pure read: 16-byte loads
+// over the aligned middle of g, its up-to-3 head and tail elements by the first threads.
+size_t grad_norm_blocks(size_t n) {
+  size_t blocks = (n + 255) / 256;
+  return blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
+}
+
+__global__ void __launch_bounds__(256) grad_norm_parts_kernel(const float* __restrict__ g, size_t n,
+                                                              double* __restrict__ parts) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  const size_t gid = (size_t)blockIdx.x * 256 + tid, stride = (size_t)gridDim.x * 256;
+  // head: the elements before the first 16-byte boundary (0 .. 3, at most n)
+  size_t head = ((16 - ((size_t)g & 15)) & 15) >> 2;
+  if (head > n) head = n;
+  const size_t nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
+  const float4* __restrict__ gv = reinterpret_cast<const float4*>(g + head);
+  double a = 0.0;
+  for (size_t i = gid; i < nvec; i += stride) {
+    const float4 x = gv[i];
+    a += (double)x.x * (double)x.x;
+    a += (double)x.y * (double)x.y;
+    a += (double)x.z * (double)x.z;
+    a += (double)x.w * (double)x.w;
   }
+  if (gid < head) a += (double)g[gid] * (double)g[gid];
+  if (gid < n - tail0) a += (double)g[tail0 + gid] * (double)g[tail0 + gid];
+  red[tid] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) parts[blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(256) grad_norm_finalize_kernel(const double* __restrict__ parts, int nparts,
+                                                                 float max_norm, float* __restrict__ ctl) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  const int per = (nparts + 255) / 256, i0 = tid * per, i1 = min(nparts, i0 + per);
+  double a = 0.0;
+  for (int i = i0; i < i1; ++i) a += parts[i];
+  red[tid] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double norm = sqrt(red[0]);
+    const float normf = (float)norm;
+    const bool finite = isfinite(normf);  // of the fp32 value that is reported
+    const double c = (double)max_norm / (norm + 1e-6);
+    ctl[0] = normf;
+    ctl[1] = finite ? (float)(c < 1.0 ? c : 1.0) : 0.f;
+    ctl[2] = finite ? 1.f : 0.f;
+    ctl[3] = ctl[3] + (finite ? 0.f : 1.f);
+  }
+}
+
+int grad_norm_launch(const float* g, size_t n, float max_norm, double* parts, float* ctl, hipStream_t st) {
+  const size_t blocks = grad_norm_blocks(n);
+  hipLaunchKernelGGL(grad_norm_parts_kernel, dim3(blocks), dim3(256), 0, st, g, n, parts);
+  SRMI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, parts, (int)blocks, max_norm, ctl);
+  SRMI_CHECK_LAUNCH();
+  return 0;
 }
 
 int adam_launch(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,

@@ -247,6 +247,15 @@ int ca_param_grads_batched_launch(const float* recs, const float* brecs, int nbl
 
 int adam_launch(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
                 float wd, float step_size, float bc2_sqrt, hipStream_t st);
+// adam_launch's step on g * ctl[1], skipped whole when ctl[2] == 0; ema (may be null):
+// ema += (1 - ema_decay) (p' - ema) in the same pass
+int adam_guarded_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, float b1, float b2,
+                        float eps, float wd, float step_size, float bc2_sqrt, float ema_decay, const float* ctl,
+                        hipStream_t st);
+// the L2 norm of g in fp64, fixed order: grad_norm_blocks(n) partials, then ctl[4] =
+// (norm, clip coefficient, finite, running count of non-finite norms)
+size_t grad_norm_blocks(size_t n);
+int grad_norm_launch(const float* g, size_t n, float max_norm, double* parts, float* ctl, hipStream_t st);
 
 struct PackEntry {
   long long w_off;   // offset of the fp32 weight [Cout][Cin][3][3] in the param buffer

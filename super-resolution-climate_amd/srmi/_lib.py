@@ -94,6 +94,10 @@ _SIGS = {
                           P], C.c_int),
     "srmi_adam_step": ([P, P, P, P, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, P],
                        C.c_int),
+    "srmi_grad_norm_workspace": ([C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_grad_norm": ([P, C.c_size_t, C.c_float, P, C.c_size_t, P, P], C.c_int),
+    "srmi_adam_step_guarded": ([P, P, P, P, P, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                C.c_float, C.c_float, P, P], C.c_int),
     "srmi_conv3x3": ([P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P,
                       C.c_float, C.c_int, P], C.c_int),
     "srmi_conv3x3_nstrips": ([C.c_int, C.c_int], C.c_int),

@@ -109,3 +109,44 @@ def checkpoint(epoch: int, itime: int, flat, table, m, v, step, lr, betas, eps, 
     """The dict CheckpointManager.save_checkpoint writes (checkpoints.py:20)."""
     return dict(epoch=epoch, itime=itime, model_state_dict=model_state_dict(flat, table),
                 optimizer_state_dict=adam_state_dict(table, m, v, step, lr, betas, eps, wd), loss=loss)
+
+
+def optimizer_record(skipped: int, ema_decay=None, ema_warmup=None) -> Dict:
+    """The fused trainer's srmi_optimizer key beside the reference's five: what its optimizer
+    guards hold that torch.optim.Adam's state dict has no place for.  Plain Python values
+    (torch.load(weights_only=True) reads them).  CheckpointManager.load_checkpoint
+    (checkpoints.py:35-51) pops the two dicts it knows and reads the rest with .get, so a
+    reference process loads a file with this key, and with ema_state_dict, unchanged."""
+    return dict(skipped=int(skipped), ema_decay=None if ema_decay is None else float(ema_decay),
+                ema_warmup=None if ema_warmup is None else bool(ema_warmup))
+
+
+def add_optimizer_extras(state: Dict, table, skipped: int, ema_cfg=None, ema: "torch.Tensor | None" = None) -> Dict:
+    """The two keys a guarded trainer adds to checkpoint()'s dict: srmi_optimizer and, with
+    averaged weights, ema_state_dict in model_state_dict's layout."""
+    cfg = ema_cfg or {}
+    state["srmi_optimizer"] = optimizer_record(skipped, cfg.get("decay"), cfg.get("warmup"))
+    if ema is not None:
+        state["ema_state_dict"] = model_state_dict(ema, table)
+    return state
+
+
+def load_optimizer_extras(table, state: Dict, params_host: torch.Tensor, ema: "torch.Tensor | None"):
+    """-> (skipped, ema_host): validated on the host, nothing is applied.  skipped from
+    srmi_optimizer (0 for a file without it; ValueError for a record that is no dict or
+    whose count is no whole number >= 0).  ema (the trainer's flat buffer, None without
+    averaged weights: the file's ema_state_dict is then ignored and ema_host is None): the
+    file's ema_state_dict with the model dict's strict semantics, or params_host when the
+    file has none."""
+    rec = state.get("srmi_optimizer")
+    if rec is not None and not isinstance(rec, dict):
+        raise ValueError(f"srmi_optimizer: a dict, got {type(rec).__name__}")
+    skipped = 0 if rec is None else rec.get("skipped", 0)
+    if not isinstance(skipped, int) or isinstance(skipped, bool) or skipped < 0:
+        raise ValueError(f"srmi_optimizer: skipped a whole number >= 0, got {skipped!r}")
+    if ema is None:
+        return skipped, None
+    sd = state.get("ema_state_dict")
+    if sd is None:
+        return skipped, params_host.clone()
+    return skipped, load_model_state_dict(ema, table, sd, strict=True, apply=False)

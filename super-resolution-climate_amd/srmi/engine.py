@@ -382,3 +382,35 @@ def axpy(y: torch.Tensor, x: torch.Tensor, a: float = 1.0, stream=None):
 def adam_step(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None):
     call("srmi_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), int(step), float(lr), float(betas[0]),
          float(betas[1]), float(eps), float(weight_decay), stream_handle(stream))
+
+
+def grad_norm_workspace(n: int) -> int:
+    """Bytes of srmi_grad_norm's workspace for an n-element gradient (a function of n alone)."""
+    nbytes = C.c_size_t()
+    call("srmi_grad_norm_workspace", int(n), C.byref(nbytes))
+    return int(nbytes.value)
+
+
+def grad_norm(g, ctl, max_norm: float = math.inf, workspace=None, stream=None):
+    """torch.nn.utils.clip_grad_norm_'s norm and coefficient of the flat fp32 gradient g into the
+    device record ctl[4] (norm, coefficient, finite, running non-finite count; include/srmi.h),
+    in fp64 and in a fixed order.  max_norm = inf measures and guards without clipping.
+    workspace: a device buffer of grad_norm_workspace(g.numel()) bytes (default: a new one).
+    Nothing is read back."""
+    assert g.dtype == ctl.dtype == torch.float32 and ctl.numel() >= 4
+    if workspace is None:
+        workspace = torch.empty(grad_norm_workspace(g.numel()), dtype=torch.uint8, device=g.device)
+    call("srmi_grad_norm", ptr(g), g.numel(), float(max_norm), ptr(workspace),
+         workspace.numel() * workspace.element_size(), ptr(ctl), stream_handle(stream))
+    return ctl
+
+
+def adam_step_guarded(p, g, m, v, ctl, step: int, lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                      ema=None, ema_decay: float = 0.0, stream=None):
+    """adam_step on g * ctl[1], a launch that writes nothing when ctl[2] == 0; ema (a flat fp32
+    buffer, or None): ema += (1 - ema_decay) (p_new - ema) in the same pass.  A skipped step
+    still consumes its step number: the caller goes on to step + 1."""
+    assert ema is None or (ema.numel() == p.numel() and ema.dtype == torch.float32)
+    call("srmi_adam_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), int(step), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(ema_decay), ptr(ctl),
+         stream_handle(stream))

@@ -133,11 +133,15 @@ class LossRecords:
         return os.path.join(d, f"{self.dataset}_{self.task}_{self.model}_losses.csv")
 
     @staticmethod
-    def serialize(tset: str, epoch: float, loss: float, ref_loss: float) -> List[str]:
-        return [_tset(tset), f"{epoch:.3f}", f"{loss:.6f}", f"{ref_loss:.6f}"]  # ResultRecord.serialize
+    def serialize(tset: str, epoch: float, loss: float, ref_loss: float, skipped: int = 0) -> List[str]:
+        """ResultRecord.serialize's four fields; skipped > 0 (steps of this record that a guarded
+        trainer skipped for a non-finite gradient norm) rides behind them in the same line."""
+        rec = [_tset(tset), f"{epoch:.3f}", f"{loss:.6f}", f"{ref_loss:.6f}"]  # ResultRecord.serialize
+        return rec + [f"skipped={int(skipped)}"] if skipped else rec
 
-    def record_losses(self, tset: str, epoch: float, loss: float, ref_loss: float, flush: bool = False) -> None:
-        self.results.append(self.serialize(tset, epoch, loss, ref_loss))
+    def record_losses(self, tset: str, epoch: float, loss: float, ref_loss: float, flush: bool = False,
+                      skipped: int = 0) -> None:
+        self.results.append(self.serialize(tset, epoch, loss, ref_loss, skipped))
         if flush:
             self.flush()
 
@@ -226,7 +230,15 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
 
     Tiles with land need nothing here: a TimesliceFeed(land=True) returns raw tiles
     whose NaN are the mask, its prepare() normalises them over their wet pixels, and a
-    FusedTrainer(land=True) steps them; this loop only slices and passes them on."""
+    FusedTrainer(land=True) steps them; this loop only slices and passes them on.
+
+    A trainer with its optimizer guard on (FusedTrainer(guard= / clip_norm= / ema=)): a batch
+    whose gradient norm is not finite leaves the weights alone and its loss is non-finite by
+    construction, so the time-slice loss (and the interp baseline) is the mean over the
+    batches whose step was NOT skipped (NaN if all were), formed on the device; the one host
+    read per time slice also fetches trainer.skipped_steps()'s counter, the steps skipped
+    during the slice go into its loss record's line, and the result holds the total as
+    "skipped".  With the guard off nothing here changes."""
     from .batch import xyflip_index
     from .dist import DistInfo, barrier, broadcast_ints, shard_capacity, shard_range
     info = getattr(trainer, "info", None) or DistInfo()
@@ -236,6 +248,8 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
         raise ValueError(f"trainer batch {trainer.batch} < the {shard_capacity(batch_size, info)}-tile shard of "
                          f"a {batch_size}-tile batch over {info.world} ranks")
     epoch0, itime0, epoch_loss, interp_l = 1, 0, 0.0, 0.0
+    guard = bool(getattr(trainer, "guard", False))
+    skipped = 0
     if refresh_state:
         if lead:
             if store is not None:
@@ -254,6 +268,8 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
         itime0 = state.get("itime", 0)
         epoch_loss = state.get("loss", float("inf"))
         nepochs += epoch0
+    if guard:
+        skipped = trainer.skipped_steps()  # (a resumed count)
     nts = len(timeslices)
     for epoch in range(epoch0, nepochs):
         for itime in range(itime0, nts):
@@ -265,7 +281,7 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
                 starts = starts + ([xyflip_index(xyflip, rng) for _ in range(nb)] if lead else [0] * nb)
             starts = broadcast_ints(starts, info, dev)  # rank 0's order on every rank
             starts, flips = starts[:nb], starts[nb:]
-            losses, ilosses = [], []
+            losses, ilosses, kept = [], [], []
             for ib, start in enumerate(starts):
                 gb = min(batch_size, ntiles - start)
                 a, e = shard_range(gb, info) if info.enabled else (0, gb)
@@ -278,15 +294,26 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
                     out = trainer.step(batch)
                 losses.append(out["loss"].clone())  # (views of the trainer's loss record)
                 ilosses.append(out["interp_loss"].clone())
+                if guard:
+                    kept.append(out["step_skipped"].clone())  # 1.0: the step was taken
             # accumulate_loss: mean of the batch losses (one host sync per time slice)
-            epoch_loss = float(torch.cat(losses).double().mean()) if losses else math.nan
-            interp_l = float(torch.cat(ilosses).double().mean()) if ilosses else math.nan
+            slice_skipped = 0
+            if guard and losses:  # over the steps that were taken; the skipped count in the same read
+                k = torch.cat(kept).double()
+                means = [torch.where(k > 0, torch.cat(x).double(), torch.zeros_like(k)).sum() / k.sum()
+                         for x in (losses, ilosses)]
+                epoch_loss, interp_l, total = torch.stack(means + [trainer.ctl[3].double()]).tolist()
+                slice_skipped, skipped = int(total) - skipped, int(total)
+            else:
+                epoch_loss = float(torch.cat(losses).double().mean()) if losses else math.nan
+                interp_l = float(torch.cat(ilosses).double().mean()) if ilosses else math.nan
             if lead:
                 if store is not None:
                     store.save(trainer, epoch, itime, "train", epoch_loss)
                 if records is not None:
                     records.record_losses("train", epoch - 1 + itime / nts, epoch_loss, interp_l,
-                                          flush=((itime + 1) % LOSSREC_FLUSH_PERIOD == 0))
+                                          flush=((itime + 1) % LOSSREC_FLUSH_PERIOD == 0),
+                                          **({"skipped": slice_skipped} if slice_skipped else {}))
             if store is not None:
                 barrier(info, dev)  # the checkpoint is complete before any rank goes on
         if on_epoch_end is not None:
@@ -295,4 +322,6 @@ def train_timeslices(trainer, timeslices: Sequence[Callable[[], torch.Tensor]], 
     if records is not None and lead:
         records.flush()
     barrier(info, dev)
+    if guard:
+        return {"prediction": epoch_loss, "interpolated": interp_l, "skipped": skipped}
     return {"prediction": epoch_loss, "interpolated": interp_l}

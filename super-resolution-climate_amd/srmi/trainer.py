@@ -27,8 +27,10 @@ from . import checkpoint as ckpt
 from ._lib import SRMI_LOSS_MEAN, SRMI_LOSS_RMSE, TILE_LOSS_SUB, call, ptr
 from .config import check_fused_task, data_downsample_factor, interp_mode
 from .dist import DistInfo, GradReducer, allreduce_sum_
-from .engine import Engine, NetSpec, adam_step, axpy, downsample, engine_stream, interp_size, upsample
+from .engine import (Engine, NetSpec, adam_step, adam_step_guarded, axpy, downsample, engine_stream, grad_norm,
+                     grad_norm_workspace, interp_size, upsample)
 from .consistency import ConsistencyLayer
+from .optim import check_clip_norm, check_ema, check_guard, ema_decay_at, make_lr_schedule
 from .spectra import SpectralLoss, check_spectral_loss_config
 from .superres import check_consistent
 
@@ -74,7 +76,9 @@ class FusedTrainer:
                  info: Optional[DistInfo] = None, device: Optional[torch.device] = None, seed: int = 0,
                  params: Optional[torch.Tensor] = None, micro: Optional[int] = None, loss_fn: str = "l2",
                  cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
-                 land: bool = False, spectral: Optional[Mapping] = None, consistent: int = 0):
+                 land: bool = False, spectral: Optional[Mapping] = None, consistent: int = 0,
+                 clip_norm: Optional[float] = None, guard: Optional[bool] = None, ema: Optional[Mapping] = None,
+                 lr_schedule=None):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -115,7 +119,38 @@ class FusedTrainer:
         a task.target_variables selection, an even scale (>= 4 under a bicubic downsample)
         and bilinear / bicubic modes: ValueError otherwise, before anything is allocated.
         K is no parameter and is not stored in a checkpoint: pass the same K to
-        TiledInference / RegionSuperResolver.  consistent=0 is the trainer as it was."""
+        TiledInference / RegionSuperResolver.  consistent=0 is the trainer as it was.
+        clip_norm, guard, ema, lr_schedule (no reference counterpart; DESIGN.md §1 "Optimizer
+        guards"; srmi.optim holds the checks and closed forms).  All opt-in: at their defaults
+        the step enqueues exactly what it did without them.
+        guard: before Adam, srmi_grad_norm takes the L2 norm of the whole-batch gradient
+        (self.grads after the micro-batch sum and, data parallel, after the all-reduces: every
+        rank derives the same numbers from the same bytes, no further collective) into the
+        device record self.ctl = (norm, clip coefficient, finite, skipped count), and Adam is
+        srmi_adam_step_guarded: a step whose norm is not finite writes nothing -- params, m, v
+        and ema stay bit for bit -- and is counted in ctl[3] (skipped_steps()).  A skipped step
+        still consumes its step number: self.t advances and the next step's bias corrections
+        are those of t + 1, because the host never reads ctl inside step().  step() then also
+        returns "grad_norm" (a view of ctl[0:1]) and "step_skipped" (ctl[2:3]: 0.0 = skipped).
+        Default None: on iff clip_norm or ema is set; guard=True alone measures and guards
+        without clipping (max_norm = inf).
+        clip_norm: None or a finite float > 0, torch.nn.utils.clip_grad_norm_'s max_norm: the
+        gradient enters Adam as g * min(1, clip_norm / (norm + 1e-6)), the coefficient read from
+        the device by the Adam launch.
+        ema: None or dict(decay=0.999, warmup=True): self.ema, a flat fp32 copy of the initial
+        params, follows ema += (1 - d_t) (params - ema) inside the Adam launch, d_t =
+        min(decay, (1 + t) / (10 + t)) at Adam step t under warm-up, else decay
+        (ema_state_dict(), eval_params(ema=True)).  Unknown keys or a decay outside [0, 1):
+        ValueError.
+        lr_schedule: None, dict(kind="constant" | "step" | "cosine", ...) or a callable
+        t0 -> lr (srmi.optim.make_lr_schedule): Adam step t runs at schedule(t - 1), a pure
+        function of the step count, so a resume with the same arguments is exact and nothing
+        of it is stored; the checkpoint's param_groups[0]["lr"] stays the base rate `lr`."""
+        # the optimizer guards' arguments: refused before anything is allocated
+        self.clip_norm = check_clip_norm(clip_norm)
+        self.ema_cfg = check_ema(ema)
+        self.guard = check_guard(guard, self.clip_norm, self.ema_cfg)
+        self.lr_schedule = make_lr_schedule(lr_schedule, lr)
         if loss_fn not in LOSS_KINDS:  # single_product_loss, dual_trainer.py:210-211
             raise ValueError(f"Unknown single-product loss function {loss_fn}")
         if task is None:
@@ -185,6 +220,12 @@ class FusedTrainer:
         self.v = torch.zeros_like(self.grads)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.t = 0
+        # the guards' control record (norm, coefficient, finite, skipped), the norm's partials
+        # and the averaged weights; none of them exists with the guards off
+        self.ctl = torch.zeros(4, dtype=torch.float32, device=self.device) if self.guard else None
+        self.norm_ws = (torch.empty(grad_norm_workspace(n), dtype=torch.uint8, device=self.device)
+                        if self.guard else None)
+        self.ema = self.params.clone() if self.ema_cfg is not None else None
         self.interp_loss = interp_loss
         C, h, w, s = spec.nchannels_in, lr_hw[0], lr_hw[1], spec.scale
         self.lrbuf = torch.empty((batch, C, h, w), dtype=torch.float32, device=self.device)
@@ -475,7 +516,14 @@ class FusedTrainer:
         for st in self.streams[1:]:
             main.wait_stream(st)
         self.t += 1
-        adam_step(self.params, self.grads, self.m, self.v, self.t, self.lr, self.betas, self.eps, self.wd)
+        lr = self.lr if self.lr_schedule is None else float(self.lr_schedule(self.t - 1))
+        if self.guard:  # norm -> ctl on the device -> the guarded step reads it there: no host read
+            grad_norm(self.grads, self.ctl, math.inf if self.clip_norm is None else self.clip_norm, self.norm_ws)
+            adam_step_guarded(self.params, self.grads, self.m, self.v, self.ctl, self.t, lr, self.betas, self.eps,
+                              self.wd, ema=self.ema,
+                              ema_decay=ema_decay_at(self.ema_cfg, self.t) if self.ema is not None else 0.0)
+        else:
+            adam_step(self.params, self.grads, self.m, self.v, self.t, lr, self.betas, self.eps, self.wd)
         for k, eng in enumerate(self.engines):
             if k:
                 self.streams[k].wait_stream(main)
@@ -484,9 +532,36 @@ class FusedTrainer:
         for st in self.streams[1:]:
             main.wait_stream(st)
         if self.spectral is not None:
-            return {"loss": self.spectral.total, "interp_loss": self.iloss4[3:4], "pixel_loss": self.loss4[3:4],
-                    "spectral_loss": self.spectral.spec4[3:4]}
-        return {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
+            out = {"loss": self.spectral.total, "interp_loss": self.iloss4[3:4], "pixel_loss": self.loss4[3:4],
+                   "spectral_loss": self.spectral.spec4[3:4]}
+        else:
+            out = {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
+        if self.guard:
+            out["grad_norm"] = self.ctl[0:1]
+            out["step_skipped"] = self.ctl[2:3]
+        return out
+
+    def current_lr(self) -> float:
+        """The learning rate the next step will use: schedule(t), the base rate without one."""
+        return self.lr if self.lr_schedule is None else float(self.lr_schedule(self.t))
+
+    def skipped_steps(self) -> int:
+        """Steps skipped so far for a non-finite gradient norm (ctl[3]).  One host
+        synchronisation: the caller's to take, outside step().  0 with the guard off."""
+        return int(self.ctl[3].item()) if self.guard else 0
+
+    def eval_params(self, ema: bool = False) -> torch.Tensor:
+        """The flat device buffer a TiledInference / RegionSuperResolver packs from: the
+        averaged weights (ema=True; ValueError on a trainer without them) or the last iterate."""
+        if ema and self.ema is None:
+            raise ValueError("eval_params(ema=True) on a trainer built without ema=")
+        return self.ema if ema else self.params
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """Reference-format state_dict of the averaged weights (CPU copies)."""
+        if self.ema is None:
+            raise ValueError("ema_state_dict() on a trainer built without ema=")
+        return ckpt.model_state_dict(self.ema, self.eng.table)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """Reference-format model state_dict (CPU copies)."""
@@ -494,9 +569,15 @@ class FusedTrainer:
 
     def checkpoint(self, epoch: int = 0, itime: int = 0, loss: float = 0.0) -> Dict:
         """What CheckpointManager.save_checkpoint writes (checkpoints.py:18-26): model
-        and torch.optim.Adam state dicts in the reference's layouts."""
-        return ckpt.checkpoint(epoch, itime, self.params, self.eng.table, self.m, self.v, self.t, self.lr,
-                               self.betas, self.eps, self.wd, loss)
+        and torch.optim.Adam state dicts in the reference's layouts.  param_groups[0]["lr"] is
+        the BASE rate whatever the schedule.  With the guard on, two more top-level keys, which
+        the reference's loader never looks at: srmi_optimizer = dict(skipped, ema_decay,
+        ema_warmup) and, with ema, ema_state_dict in model_state_dict's layout."""
+        state = ckpt.checkpoint(epoch, itime, self.params, self.eng.table, self.m, self.v, self.t, self.lr,
+                                self.betas, self.eps, self.wd, loss)
+        if self.guard:
+            ckpt.add_optimizer_extras(state, self.eng.table, self.skipped_steps(), self.ema_cfg, self.ema)
+        return state
 
     def load_checkpoint(self, state: Dict) -> None:
         """Resume from a reference-format checkpoint dict (checkpoints.py:35-51,
@@ -505,18 +586,27 @@ class FusedTrainer:
         strict semantics (common.py:50-71: unexpected or missing keys raise, only a
         re-shaped 'tail' is skipped).  Both dicts are validated into host buffers
         before anything on the device changes, so a failed load leaves the trainer
-        as it was."""
+        as it was -- the averaged weights and the skipped count too: a trainer with ema
+        loads ema_state_dict (strict, as the model's) or, from a file without one, starts
+        the average at the loaded params; a trainer without ema ignores the key; the count
+        comes from srmi_optimizer (0 without it)."""
         host_p = ckpt.load_model_state_dict(self.params, self.eng.table, state["model_state_dict"], strict=True,
                                             apply=False)
         t, hp, mh, vh = ckpt.load_adam_state_dict(self.eng.table, state["optimizer_state_dict"], self.m, self.v,
                                                   apply=False)
+        skipped, host_e = ckpt.load_optimizer_extras(self.eng.table, state, host_p, self.ema)
         self.params.copy_(host_p)
+        if self.ema is not None:
+            self.ema.copy_(host_e)
+        if self.guard:
+            self.ctl.zero_()
+            self.ctl[3] = float(skipped)
         self.m.copy_(mh)
         self.v.copy_(vh)
         self.t = t
         self.lr, self.betas, self.eps, self.wd = hp["lr"], tuple(hp["betas"]), hp["eps"], hp["weight_decay"]
         if self.info.enabled:
-            for x in (self.params, self.m, self.v):
+            for x in (self.params, self.m, self.v) + ((self.ema,) if self.ema is not None else ()):
                 torch.distributed.broadcast(x, 0)
         for e in self.engines:
             e.pack(self.params)
