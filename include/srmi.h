@@ -72,6 +72,12 @@
  *                                   with its per-pixel map, and the mean square error that
  *                                   PSNR needs.  No reference counterpart: the reference
  *                                   scores a field by its RMSE alone.
+ *   srmi_distribution_workspace,
+ *   srmi_distribution            -> histograms of a prediction and of a truth on the truth's
+ *                                   range, their joint histogram, and the Perkins score,
+ *                                   Wasserstein-1 distance and quantiles formed from them.
+ *                                   No reference counterpart: the reference scores a field
+ *                                   by its RMSE alone.
  *   srmi_spectral_loss_workspace,
  *   srmi_spectral_loss_parts,
  *   srmi_spectral_loss_from_parts,
@@ -722,6 +728,58 @@ int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int
 int srmi_ssim_workspace(int C, int H, int W, size_t* bytes);
 int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_range, void* workspace,
               size_t workspace_bytes, float* out, long long* count, float* map, void* stream);
+
+/* ---- the distribution score (no reference counterpart) ------------------- */
+/* Does the prediction a have the truth b's distribution of values?  Both [C][H][W] fp32 on
+ * the device, possibly with NaN / Inf, per channel; tests/distribution_oracle.py restates it
+ * in numpy.  B = nbins in 2 .. 4096, J = njoint in 0 .. 64 (0: no joint histogram).
+ *   Used pixel: finite in a and in b.  N is their count.
+ *   Range: lo, hi = the min and max of b over the used pixels (exact: they do not depend on
+ *   the order of the reduction), or lo_hi[0], lo_hi[1] where lo_hi (a HOST pointer to two
+ *   floats, finite, hi > lo) is given.  scale = hi > lo ? fp32(B) / (hi - lo) : 0, the
+ *   subtraction and the division each rounded once, correctly, in fp32.
+ *   Bin of a value x, an index into B + 2 entries: 0 (under) if x < lo; B + 1 (over) if
+ *   x > hi; B if x == hi (what the formula gives whenever hi > lo, and the bin of every used
+ *   pixel of b when hi == lo); otherwise 1 + min((int)t, B - 1) with t = (x - lo) * scale in
+ *   fp32 -- one subtraction, one multiplication, truncation.  The comparisons decide under and
+ *   over before any conversion and the converted value is clamped as an integer, so no input
+ *   indexes outside the table.  With the range b's own, b has no under and no over.
+ *   Joint bin: ja, jb = the same formula with J in place of B (its own scale fp32(J) / (hi -
+ *   lo)), minus 1, clamped into 0 .. J - 1: a prediction outside the range goes to the edge
+ *   bin.  The count goes to joint[c][ja][jb].
+ * hist [C][2][B + 2] int64 (0: a, 1: b), joint [C][J][J] int64 (may be NULL when J == 0), range
+ * [C][2] fp32 = {lo, hi} (NaN, NaN for a channel without a used pixel), count [C] int64 = N,
+ * derived [C][4 + 2 nprobs] fp64 = {pss, w1, under, over, q_a[nprobs], q_b[nprobs]}, formed by
+ * the last launch from the int64 tables alone, with w = (hi - lo) / B in fp64:
+ *   pss = sum_k min(ha[k], hb[k]) / N (Perkins et al. 2007), the sum an integer;
+ *   w1 = w * sum_k |cumA[k] - cumB[k]| / N over the B + 2 entries, the sum an integer: the
+ *   Wasserstein-1 distance of the two histograms with under and over taken as bins of one
+ *   width beside the range -- a LOWER bound on the fields' distance when a leaves the range;
+ *   under = ha[0] / N, over = ha[B + 1] / N;
+ *   the quantile at probs[i] (HOST array, nprobs in 0 .. 16, each strictly inside (0, 1);
+ *   passed to the kernel by value): r = p N in fp64, k the smallest entry with cum[k] >= r,
+ *   value = left(k) + w (r - cum[k - 1]) / h[k], left(k) = lo + (k - 1) w, so that under
+ *   spans [lo - w, lo] and over [hi, hi + w].
+ *   N == 0: every entry of derived is NaN.
+ * Every count is an integer sum, so the result is exact and bit-identical from run to run.
+ * Launches on `stream`: range partials (skipped when lo_hi is given), histogram partials
+ * (LDS integer atomics, one int32 table per workgroup, plain stores), finish (the tables in
+ * workgroup order, then the derived values).  No global atomics, no host synchronisation, no allocation: capturable.
+ * srmi_distribution_workspace (host only) gives the bytes of `workspace` (16-byte aligned; it
+ * need not be initialised).  No alignment requirement on a or b; H, W >= 1 with H W <= 2^31
+ * - 1.  flags: 0, or SRMI_DISTRIBUTION_* bits that select the measured alternatives of the
+ * histogram kernel (DESIGN.md "Distribution score"); the result does not depend on them.
+ * A missing a, b, workspace, hist, range, count or derived (joint with J > 0, probs with
+ * nprobs > 0), a workspace that is too small or not aligned, B, J, nprobs or a probability out
+ * of range (NaN included), a lo_hi that is not finite with hi > lo, unknown flags, C < 1, H or
+ * W < 1 or H W > 2^31 - 1: SRMI_ERR_ARG, and nothing is launched. */
+#define SRMI_DISTRIBUTION_MERGE_RUNS 1   /* a lane adds a run of equal bins among its 8 pixels once */
+#define SRMI_DISTRIBUTION_ONE_COPY 2     /* one copy of the tables per workgroup */
+#define SRMI_DISTRIBUTION_COPY_BY_WAVE 4 /* the copy chosen by the wave, not by the lane */
+int srmi_distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes);
+int srmi_distribution(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
+                      const double* probs, int nprobs, void* workspace, size_t workspace_bytes, long long* hist,
+                      long long* joint, float* range, long long* count, double* derived, int flags, void* stream);
 
 /* ---- consistency with the coarse input (no reference counterpart) -------- */
 /* Iterative back-projection x <- x + U(lr - D x) of an HR field x [C][h s][w s] onto the LR

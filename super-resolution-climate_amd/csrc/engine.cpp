@@ -1681,6 +1681,17 @@ int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_ra
   return ssim_launch(a, b, C, H, W, data_range, workspace, workspace_bytes, out, count, map, S_(stream));
 }
 
+int srmi_distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes) {
+  return distribution_workspace(C, H, W, nbins, njoint, bytes);
+}
+
+int srmi_distribution(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
+                      const double* probs, int nprobs, void* workspace, size_t workspace_bytes, long long* hist,
+                      long long* joint, float* range, long long* count, double* derived, int flags, void* stream) {
+  return distribution_launch(a, b, C, H, W, nbins, njoint, lo_hi, probs, nprobs, workspace, workspace_bytes, hist,
+                             joint, range, count, derived, flags, S_(stream));
+}
+
 int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
   return spectral_loss_workspace(nplanes, H, W, P, Q, bytes);
 }

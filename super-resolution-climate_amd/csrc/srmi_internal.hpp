@@ -337,6 +337,11 @@ int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, i
 int ssim_workspace(int C, int H, int W, size_t* bytes);
 int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_range, void* ws, size_t ws_bytes,
                 float* out, long long* count, float* map, hipStream_t st);
+// the distribution score: histograms, joint histogram and quantiles of two fields (distribution.hip)
+int distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes);
+int distribution_launch(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
+                        const double* probs, int nprobs, void* ws, size_t ws_bytes, long long* hist, long long* joint,
+                        float* range, long long* count, double* derived, int flags, hipStream_t st);
 // the spectral loss term of the training step (spectral_loss.hip)
 int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
 int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,

@@ -334,6 +334,106 @@ def load_ssim(path: str) -> Tuple[Dict[str, np.ndarray], List[str]]:
         return out, names.split(",") if names else []
 
 
+DISTRIBUTION_SCALARS = ("pss", "w1", "under", "over")
+DISTRIBUTION_QUANTILES = ("q_pred", "q_truth", "q_bias")
+DISTRIBUTION_TABLES = ("hist_pred", "hist_truth")
+
+
+def save_distribution(path: str, dist: Dict[str, object], varnames: Sequence[str],
+                      probs: Sequence[float]) -> str:
+    """One distribution score (the dict of srmi.distribution.DistributionScore.measure, e.g.
+    one entry of RegionSuperResolver.score_distribution's third result) as a netCDF-3 file,
+    through the same scipy writer.  The counts -- 'hist_pred', 'hist_truth' on ('channel',
+    'entry'), 'joint' on ('channel', 'jpred', 'jtruth') when it has bins, 'count' on
+    ('channel',) -- are float64: netCDF-3 has no int64, and a double holds every count below
+    2^53 exactly (a count is at most H W < 2^31).  'lo', 'hi' are float32; 'pss', 'w1',
+    'under', 'over' float64 on ('channel',); 'q_pred', 'q_truth', 'q_bias' float64 on
+    ('channel', 'prob') with the coordinate 'prob'; 'edges' float64 on ('channel', 'edge'),
+    the B + 3 edges of the B + 2 entries (srmi.distribution.bin_edges).  The attribute
+    ``varnames`` holds the channel names joined by ``,``, as loss_keys does.  No reference
+    counterpart."""
+    from scipy.io import netcdf_file
+
+    from .distribution import bin_edges
+    keys = DISTRIBUTION_SCALARS + DISTRIBUTION_QUANTILES + DISTRIBUTION_TABLES + ("joint", "lo", "hi", "count")
+    missing = [k for k in keys if k not in dist]
+    if missing:
+        raise ValueError(f"dist lacks {missing}")
+    n, pr = len(varnames), np.asarray(list(probs), dtype=np.float64)
+    tables = {q: np.ascontiguousarray(_np(dist[q]).astype(np.int64)) for q in DISTRIBUTION_TABLES + ("joint", "count")}
+    nb2 = tables["hist_pred"].shape[-1]
+    J = tables["joint"].shape[-1]
+    for q, shape in (("hist_pred", (n, nb2)), ("hist_truth", (n, nb2)), ("joint", (n, J, J)), ("count", (n,))):
+        if tables[q].shape != shape:
+            raise ValueError(f"{q}: {tables[q].shape} is not {shape}")
+        if tables[q].size and int(tables[q].max()) >= 2 ** 53:
+            raise ValueError(f"{q}: a count of 2^53 or more does not fit a double")
+    if nb2 < 4:
+        raise ValueError(f"hist_pred: {nb2} entries are fewer than 2 bins and the two outer entries")
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        f.bins = np.int32(nb2 - 2)
+        f.createDimension("channel", n)
+        f.createDimension("entry", nb2)
+        f.createDimension("edge", nb2 + 1)
+        if len(pr):
+            f.createDimension("prob", len(pr))
+            pv = f.createVariable("prob", np.float64, ("prob",))
+            pv[:] = pr
+        for q in DISTRIBUTION_TABLES:
+            dv = f.createVariable(q, np.float64, ("channel", "entry"))
+            dv[:] = tables[q].astype(np.float64)
+        if J:
+            f.createDimension("jpred", J)
+            f.createDimension("jtruth", J)
+            dv = f.createVariable("joint", np.float64, ("channel", "jpred", "jtruth"))
+            dv[:] = tables["joint"].astype(np.float64)
+        dv = f.createVariable("count", np.float64, ("channel",))
+        dv[:] = tables["count"].astype(np.float64)
+        lohi = {}
+        for q in ("lo", "hi"):
+            lohi[q] = np.ascontiguousarray(_np(dist[q]).astype(np.float32))
+            if lohi[q].shape != (n,):
+                raise ValueError(f"{q}: {lohi[q].shape} is not {(n,)}")
+            dv = f.createVariable(q, np.float32, ("channel",))
+            dv._FillValue = np.array([np.nan], dtype=np.float32)
+            dv[:] = lohi[q]
+        ev = f.createVariable("edges", np.float64, ("channel", "edge"))
+        ev._FillValue = np.array([np.nan], dtype=np.float64)
+        ev[:] = bin_edges(lohi["lo"], lohi["hi"], nb2 - 2)
+        for q in DISTRIBUTION_SCALARS + (DISTRIBUTION_QUANTILES if len(pr) else ()):
+            a = np.ascontiguousarray(_np(dist[q]).astype(np.float64))
+            shape = (n,) if q in DISTRIBUTION_SCALARS else (n, len(pr))
+            if a.shape != shape:
+                raise ValueError(f"{q}: {a.shape} is not {shape}")
+            dv = f.createVariable(q, np.float64, ("channel",) if q in DISTRIBUTION_SCALARS else ("channel", "prob"))
+            dv._FillValue = np.array([np.nan], dtype=np.float64)
+            dv[:] = a
+    return path
+
+
+def load_distribution(path: str) -> Tuple[Dict[str, np.ndarray], List[str], np.ndarray]:
+    """The inverse of save_distribution: (the score as numpy arrays, the counts int64 again,
+    with 'edges' beside them; varnames; probs)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        n = f.dimensions["channel"]
+        pr = np.array(f.variables["prob"][:], dtype=np.float64) if "prob" in f.variables else np.zeros(0)
+        out = {q: np.array(f.variables[q][:]).astype(np.int64) for q in DISTRIBUTION_TABLES + ("count",)}
+        out["joint"] = (np.array(f.variables["joint"][:]).astype(np.int64) if "joint" in f.variables
+                        else np.zeros((n, 0, 0), dtype=np.int64))
+        for q in ("lo", "hi"):
+            out[q] = np.array(f.variables[q][:], dtype=np.float32)
+        for q in DISTRIBUTION_SCALARS + ("edges",):
+            out[q] = np.array(f.variables[q][:], dtype=np.float64)
+        for q in DISTRIBUTION_QUANTILES:
+            out[q] = np.array(f.variables[q][:], dtype=np.float64) if len(pr) else np.zeros((n, 0))
+        return out, names.split(",") if names else [], pr
+
+
 def load_spectra(path: str) -> Tuple[Dict[str, np.ndarray], int, List[str]]:
     """The inverse of save_spectra: (spectra as numpy arrays, window, varnames)."""
     from scipy.io import netcdf_file

@@ -345,6 +345,7 @@ class RegionSuperResolver:
         self._graph = None
         self._spectra = {}  # (window, stride) -> the SpectralScore of each image (score_spectra)
         self._ssim = {}  # (data_range, maps) -> the SSIMScore of each image (score_ssim)
+        self._distribution = {}  # (bins, joint, probs, value_range) -> the DistributionScore of each image
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -550,6 +551,37 @@ class RegionSuperResolver:
             self._ssim[key] = {name: SSIMScore((self.C, self.h * s, self.w * s), data_range, maps, device=self.device)
                                for name in ("model", "interpolated")}
         return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._ssim[key].items()}
+
+    def score_distribution(self, hr_region: torch.Tensor, bins: int = 256, joint: int = 32,
+                           probs=(0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999), value_range=None):
+        """``score``, then the distribution score (srmi.distribution.DistributionScore) of
+        'model' and of 'interpolated' against hr_region: (images, losses, {'model': ...,
+        'interpolated': ...}), each entry the dict of DistributionScore.measure -- per channel
+        the histograms of the image and of the truth on the truth's range ('hist_pred',
+        'hist_truth', 'lo', 'hi'), their joint histogram ('joint', which
+        srmi.distribution.contingency turns into hits and misses above a threshold), 'count',
+        the Perkins score 'pss', the Wasserstein-1 distance 'w1', the shares 'under' and
+        'over' of the image outside the truth's range, and the quantiles 'q_pred', 'q_truth'
+        with 'q_bias', the number that shows output pulled to the mean: positive at low
+        probabilities and negative at high ones.  bins, joint, probs, value_range: as
+        DistributionScore takes them.  images and losses are ``score``'s, bit for bit; the
+        entries are views valid until the next call with the same arguments.  No host
+        synchronisation.  With graph=True the score is measured after the replay, outside the
+        captured graph.
+
+        land=True: the NaN of the image and of hr_region are the mask, pixel by pixel
+        ('count' is what is left)."""
+        from .distribution import DistributionScore
+        s = self.s
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        key = (int(bins), int(joint), tuple(float(p) for p in probs),
+               None if value_range is None else tuple(float(v) for v in value_range))
+        if key not in self._distribution:
+            self._distribution[key] = {name: DistributionScore((self.C, self.h * s, self.w * s), bins, joint, probs,
+                                                               value_range, device=self.device)
+                                       for name in ("model", "interpolated")}
+        return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._distribution[key].items()}
 
     def set_params(self, params: torch.Tensor) -> None:
         """Load new weights: copied into the parameter buffer the engines (and the

@@ -46,6 +46,21 @@ time of the numpy oracle (tests/ssim_oracle.py, fp64 and fp32) on the host for t
 pairs of fields, run once, with the device's largest deviation from the fp64 oracle next to
 e32, the fp32 oracle's; writes profiles/ssim_bench.json.  No pass / fail bar.
 
+--distribution: what does the distribution score cost, and on which data?  One
+RegionSuperResolver at the last of --overlaps scores a synthetic HR truth: ``score``,
+``score_distribution`` and, window by window in turn on one device, the score's launches alone
+(two DistributionScore.measure per stage) beside the SSIM stage (two SSIMScore.measure), on
+three inputs because a histogram's cost depends on the data: the tool's two images against
+its synthetic truth (white Gaussian noise; the images are smooth), a smooth field (sinusoids
+as long as the region, so that a wave's pixels share a bin) and white noise, both over the
+truth's range.  Every alternative of the
+histogram kernel (one copy of the tables, the copy chosen by the wave, run merging) and
+the score with the range given (which drops the range launch) are arms of the same loop.
+Reports the median and the spread of each, the bytes/s against reading both fields once, the
+scores, and the time of the numpy oracle (tests/distribution_oracle.py) on the host for the
+same fields, run once -- the device's tables must equal its tables; writes
+profiles/distribution_bench.json.  No pass / fail bar.
+
 --ensemble K [K ...]: what does the self-ensemble cost, and what does it give?  One
 RegionSuperResolver(ensemble=K) per K in {1, 4, 8} (1 always among them) on the default
 region at the last of --overlaps, the arms alternating window by window.  Reports the HR
@@ -327,6 +342,125 @@ def ssim_main(a, spec, params, dev, kw):
     return res
 
 
+def distribution_main(a, spec, params, dev, kw):
+    import time
+
+    import numpy as np
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.distribution import COPY_BY_WAVE, MERGE_RUNS, ONE_COPY, DistributionScore
+    from srmi.ssim import SSIMScore
+    from srmi.superres import RegionSuperResolver
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import distribution_oracle as do
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    shape = (1, side, side)
+    hr = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    rs = RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                             graph=not a.no_graph, **kw)
+    for _ in range(a.warmup):
+        images, losses, dist = rs.score_distribution(hr)
+    torch.cuda.synchronize()
+    names = ("model", "interpolated")
+    # the inputs: the tool's two images against its synthetic truth (white Gaussian noise; the
+    # images are smooth), a smooth field (a few sinusoids as long as the region, the prediction
+    # pulled to the mean or shifted) and white noise, both over the truth's range
+    lo, hi = float(hr.min()), float(hr.max())
+    g = torch.Generator(device=dev).manual_seed(7)
+    wtruth = lo + (hi - lo) * torch.rand(shape, device=dev, generator=g)
+    y = torch.arange(side, device=dev, dtype=torch.float64)[:, None] / side
+    x = torch.arange(side, device=dev, dtype=torch.float64)[None, :] / side
+    t = (torch.sin(2 * math.pi * (y / 1.7 + x / 3.1)) + 0.5 * torch.sin(2 * math.pi * (y / 0.9 - x / 1.3) + 1.0)
+         + 0.25 * torch.cos(2 * math.pi * (y / 0.6 + x / 0.45)))
+    t = (t - t.min()) / (t.max() - t.min())  # 0 .. 1
+    struth = (lo + (hi - lo) * t).float()[None].contiguous()
+    pairs = {"synthetic": [(images[n].clone(), hr) for n in names],
+             "smooth": [((lo + (hi - lo) * (0.1 + 0.8 * t)).float()[None].contiguous(), struth),
+                        ((lo + (hi - lo) * (t + 0.02)).float()[None].contiguous(), struth)],
+             "white": [((wtruth + 0.05 * (hi - lo) * torch.randn(shape, device=dev, generator=g)).contiguous(), wtruth)
+                       for _ in names]}
+    variants = {"stage": 0, "one_copy": ONE_COPY, "copy_by_wave": COPY_BY_WAVE, "merge_runs": MERGE_RUNS,
+                "merge_runs_one_copy": MERGE_RUNS | ONE_COPY}
+    scorers = {k: [DistributionScore(shape, device=dev, flags=f) for _ in names] for k, f in variants.items()}
+    scorers["given_range"] = [DistributionScore(shape, value_range=(lo, hi), device=dev) for _ in names]
+    ssim = [SSIMScore(shape, device=dev) for _ in names]
+
+    def stage(scs, inp):
+        def fn():
+            for sc, (p, t) in zip(scs, pairs[inp]):
+                sc.measure(p, t)
+        return fn
+
+    runs = {"score": lambda: rs.score(hr), "score_distribution": lambda: rs.score_distribution(hr)}
+    for inp in pairs:
+        for k, scs in scorers.items():
+            runs[f"{inp}/{k}"] = stage(scs, inp)
+        runs[f"{inp}/ssim_stage"] = stage(ssim, inp)
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for k, fn in runs.items():
+            n = a.regions * (20 if "/" in k else 1)  # a window of a stage alone is many calls
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(n):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / n)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    nbytes = 2 * 2 * 4 * float(side) ** 2  # two measures: a and b read once each
+    # the numpy oracle on the same fields, run once, and the device's tables against it
+    host, summary = {}, {}
+    for inp, prs in pairs.items():
+        host[inp] = 0.0
+        for name, sc, (p, t) in zip(names, scorers["stage"], prs):
+            m = sc.measure(p, t)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            o = do.distribution(p.cpu().numpy(), t.cpu().numpy())
+            host[inp] += time.perf_counter() - t0
+            for q in ("hist_pred", "hist_truth", "joint", "count"):
+                if not np.array_equal(m[q].cpu().numpy(), o[q]):
+                    raise SystemExit(f"superres_bench: {inp} {name}: {q} differs from the oracle's")
+            err = float(np.nanmax(np.abs(sc.derived.cpu().numpy() - o["derived"])
+                                  / np.maximum(np.abs(o["derived"]), hi - lo)))
+            occupied = int((o["hist_truth"][0] > 0).sum())
+            summary[f"{inp}/{name}"] = {"pss": float(m["pss"]), "w1": float(m["w1"]), "under": float(m["under"]),
+                                        "over": float(m["over"]),
+                                        "q_bias": [float(f"{v:.5g}") for v in m["q_bias"][0].tolist()],
+                                        "derived_vs_oracle_max_rel": float(f"{err:.2e}"),
+                                        "occupied_truth_bins": occupied}
+    sc0 = scorers["stage"][0]
+    res = {"tool": "superres_bench --distribution", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 score_distribution, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR "
+                                  f"tile {a.tile}, overlap {r}; two distribution scores per call and per stage, "
+                                  f"bins {sc0.bins}, joint {sc0.joint}, {len(sc0.probs)} quantiles",
+                      "inputs": {"synthetic": "'model' and 'interpolated' against the tool's synthetic truth (white "
+                                              "Gaussian noise; the images are smooth)",
+                                 "smooth": "sinusoids as long as the region over the truth's range; the prediction "
+                                           "pulled to the mean (first score) or shifted by 2 % (second)",
+                                 "white": "uniform noise over the truth's range, the prediction that plus 5 % noise"},
+                      "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                      "regions_per_window": a.regions, "stage_calls_per_window": a.regions * 20,
+                      "workspace_mib_per_score": round(sc0.workspace.numel() / 2 ** 20, 2)},
+           "ms": {k: {"median": round(med[k], 4), "min_max": [round(min(v), 4), round(max(v), 4)]}
+                  for k, v in ms.items()},
+           "stage_bytes": int(nbytes),
+           "stage_gb_per_s": {k: round(nbytes / (med[k] * 1e-3) / 1e9, 1) for k in med if "/" in k},
+           "stage_share_of_score_distribution": round(med["synthetic/stage"] / med["score_distribution"], 5),
+           "stage_over_score": round(med["synthetic/stage"] / med["score"], 5),
+           "score_distribution_over_score": round(med["score_distribution"] / med["score"], 4),
+           "white_over_smooth": round(med["white/stage"] / med["smooth/stage"], 4),
+           "stage_over_ssim_stage": {inp: round(med[f"{inp}/stage"] / med[f"{inp}/ssim_stage"], 4) for inp in pairs},
+           "range_launch_ms": {inp: round(med[f"{inp}/stage"] - med[f"{inp}/given_range"], 4) for inp in pairs},
+           "scores": summary, "host_oracle_s": {k: round(v, 2) for k, v in host.items()}}
+    return res
+
+
 def ensemble_main(a, spec, params, lr, dev, kw):
     from oracle.rcan_oracle import synthetic_hr
     from srmi.superres import RegionSuperResolver
@@ -476,22 +610,26 @@ def main():
     ap.add_argument("--spectra", type=int, nargs="?", const=256, default=None, metavar="WINDOW",
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
     ap.add_argument("--ssim", action="store_true", help="time score_ssim's SSIM stage beside score")
+    ap.add_argument("--distribution", action="store_true",
+                    help="time score_distribution's stage beside score and the SSIM stage, on a smooth and a white input")
     ap.add_argument("--ensemble", type=int, nargs="+", default=None, metavar="K", choices=(1, 4, 8),
                     help="time RegionSuperResolver(ensemble=K) for each K (1 is always among them)")
     ap.add_argument("--consistent", type=int, nargs="+", default=None, metavar="K", choices=range(17),
                     help="time RegionSuperResolver(consistent=K) for each K (0 is always among them)")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
-                                                "spectra_bench.json, ssim_bench.json, ensemble_bench.json, "
-                                                "consistency_bench.json)")
+                                                "spectra_bench.json, ssim_bench.json, distribution_bench.json, "
+                                                "ensemble_bench.json, consistency_bench.json)")
     a = ap.parse_args()
-    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim > 1:
-        raise SystemExit("superres_bench: --land, --spectra, --ssim, --ensemble and --consistent are separate runs")
+    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution > 1:
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --distribution, --ensemble and --consistent are "
+                         "separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
                              "spectra_bench.json" if a.spectra is not None else
                              "ssim_bench.json" if a.ssim else
+                             "distribution_bench.json" if a.distribution else
                              "ensemble_bench.json" if a.ensemble is not None else
                              "consistency_bench.json" if a.consistent is not None else "superres_bench.json")
     if not torch.cuda.is_available():
@@ -509,10 +647,12 @@ def main():
     default_init_(params, table, 0)
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
-    if a.land is not None or a.spectra is not None or a.ssim or a.ensemble is not None or a.consistent is not None:
+    if (a.land is not None or a.spectra is not None or a.ssim or a.distribution or a.ensemble is not None
+            or a.consistent is not None):
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
                           ssim_main(a, spec, params, dev, kw) if a.ssim else
+                          distribution_main(a, spec, params, dev, kw) if a.distribution else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
                           consistency_main(a, spec, params, lr, dev, kw))
         print(line)
