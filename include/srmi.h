@@ -905,6 +905,60 @@ int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long 
 int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long long nplanes, int H, int W, int P, int Q,
                           float weight, const float* spec4, float* dy, void* stream);
 
+/* ---- the SSIM loss term (no reference counterpart) ---------------------- */
+/* A structural term beside the pixel loss of a training step: 1 - the mean SSIM of pred = a
+ * against target = b, both [nplanes][H][W] fp32 on the device (nplanes = N C), possibly with
+ * NaN / Inf.  Everything of "the SSIM score" above holds per plane: the 11 fp32 taps g, G = g
+ * (x) g; the valid positions only (Hv = H - 10 rows of Wv = W - 10); a position is USED iff
+ * the 121 pixels of its window are finite in a and in b of that plane; lo, hi the min / max of
+ * b's finite pixels in the plane, L = hi - lo, or data_range where data_range > 0; the pivot
+ * r = 0.5 lo + 0.5 hi (always b's); C1 = (0.01 L)^2, C2 = (0.03 L)^2.  A plane contributes no
+ * position when it has no finite target pixel or when L is 0 or not finite (a constant
+ * target).  With a' = a - r, b' = b - r (0 where a pixel is not finite in both):
+ *   m_a = G * a', m_b = G * b', s_aa = G * a'^2 - m_a^2, s_bb likewise, s_ab = G * (a' b') -
+ *   m_a m_b; mu_a = m_a + r, mu_b = m_b + r; D_l = mu_a^2 + mu_b^2 + C1, l = (2 mu_a mu_b + C1)
+ *   / D_l; D_c = s_aa + s_bb + C2, cs = (2 s_ab + C2) / D_c; ssim = l cs.
+ *   S = the sum of ssim over the used positions of all planes of the (global) batch, Nused
+ *   their number, L_ssim = 1 - S / Nused; Nused = 0: L_ssim = 0 and its gradient is 0.
+ *   Gradient (L and r are constants).  At a used position p: B_p = -2 l cs / D_c, C_p = 2 l /
+ *   D_c, A_p = 2 cs (mu_b - mu_a l) / D_l - B_p m_a - C_p m_b; A = B = C = 0 at every other
+ *   position.  dS / da (q) = (G^T * A)(q) + a'(q) (G^T * B)(q) + b'(q) (G^T * C)(q), G^T * the
+ *   zero-extended ("full") correlation of an [Hv][Wv] map back onto [H][W].  The pivoted form
+ *   is part of the definition: at 290 +- 1.5 the unpivoted terms cancel in fp32.
+ * Arithmetic: fp32 as the score's (separable, the horizontal pass first, taps ascending, FMA),
+ * every sum over positions, tiles and planes in fp64 or integers in a fixed order, no atomics:
+ * bit-identical from run to run, and the same bits whether the planes go through one call or
+ * several.
+ * srmi_ssim_loss_workspace (host only): the bytes of `workspace` (16-byte aligned, need not
+ * be initialised) for nplanes planes; it is laid out plane by plane, bytes / nplanes each, so
+ * a call over planes p0 .. p0 + n - 1 of a batch takes the batch's workspace + p0 * (bytes /
+ * nplanes).  Per plane it holds r and L, the range pass's min / max pairs, the position tiles'
+ * sums and counts, and the maps A, B, C [Hv][Wv].
+ * srmi_ssim_loss_parts: three launches (range pass, tile pass, per-plane sum).  pred, target
+ * [nplanes][H][W]; data_range: L of every plane, <= 0: the target's own range per plane;
+ * parts[nplanes]: per plane the fp64 sum of ssim over its used positions in a fixed order,
+ * rounded once to fp32; cparts[nplanes]: their count as a float (exact: H W <= 2^24).  Every
+ * element of the workspace that srmi_ssim_loss_dy reads is written here.
+ * srmi_ssim_loss_from_parts: parts and cparts [nplanes] summed over the planes of the
+ * (global) batch in fp64 in plane order; ssim4 = {S, Nused, 1 / Nused, L_ssim} (all 0 when
+ * Nused = 0) and total[0] = fma(weight, ssim4[3], base[0]).  base: one device float, the
+ * finalised pixel loss (&loss4[3]) or the spectral term's total; it is only read.
+ * srmi_ssim_loss_dy: workspace as srmi_ssim_loss_parts left it for these planes, pred and
+ * target the same fields; dy [nplanes][H][W] = fma(-weight ssim4[2], dS / da, dy), the scale
+ * read from the device, one rounding.  A pixel that is not finite in both pred and target is
+ * not written; weight == 0 launches nothing.
+ * All three: `stream`, no allocation, no host read, capturable.  SRMI_ERR_ARG, nothing
+ * launched and no output touched: H or W < 11; H W > 2^24; nplanes < 1; data_range NaN or
+ * +-Inf; weight < 0 or not finite; a missing buffer; a workspace that is too small or not
+ * 16-byte aligned. */
+int srmi_ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes);
+int srmi_ssim_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
+                         float* parts, float* cparts, void* workspace, size_t workspace_bytes, void* stream);
+int srmi_ssim_loss_from_parts(const float* parts, const float* cparts, long long nplanes, float weight,
+                              const float* base, float* ssim4, float* total, void* stream);
+int srmi_ssim_loss_dy(const void* workspace, size_t workspace_bytes, const float* pred, const float* target,
+                      long long nplanes, int H, int W, float weight, const float* ssim4, float* dy, void* stream);
+
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)
  * -> hr [B][C][T][T] = xyflip(lnorm(raw)) (norm 'lnorm' raw.py:169-181: per tile

@@ -1713,6 +1713,26 @@ int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long lo
   return spectral_loss_dy_launch(workspace, workspace_bytes, nplanes, H, W, P, Q, weight, spec4, dy, S_(stream));
 }
 
+int srmi_ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes) {
+  return ssim_loss_workspace(nplanes, H, W, bytes);
+}
+
+int srmi_ssim_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
+                         float* parts, float* cparts, void* workspace, size_t workspace_bytes, void* stream) {
+  return ssim_loss_parts_launch(pred, target, nplanes, H, W, data_range, parts, cparts, workspace, workspace_bytes,
+                                S_(stream));
+}
+
+int srmi_ssim_loss_from_parts(const float* parts, const float* cparts, long long nplanes, float weight,
+                              const float* base, float* ssim4, float* total, void* stream) {
+  return ssim_loss_from_parts_launch(parts, cparts, nplanes, weight, base, ssim4, total, S_(stream));
+}
+
+int srmi_ssim_loss_dy(const void* workspace, size_t workspace_bytes, const float* pred, const float* target,
+                      long long nplanes, int H, int W, float weight, const float* ssim4, float* dy, void* stream) {
+  return ssim_loss_dy_launch(workspace, workspace_bytes, pred, target, nplanes, H, W, weight, ssim4, dy, S_(stream));
+}
+
 int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
                            const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
                            int* nwet, void* stream) {

@@ -350,6 +350,14 @@ int spectral_loss_from_parts_launch(const float* parts, const float* cparts, lon
                                     const float* loss4, float* spec4, float* total, hipStream_t st);
 int spectral_loss_dy_launch(const void* ws, size_t ws_bytes, long long nplanes, int H, int W, int P, int Q,
                             float weight, const float* spec4, float* dy, hipStream_t st);
+// the SSIM loss term of the training step (ssim_loss.hip)
+int ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes);
+int ssim_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
+                           float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st);
+int ssim_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, float weight,
+                                const float* base, float* ssim4, float* total, hipStream_t st);
+int ssim_loss_dy_launch(const void* ws, size_t ws_bytes, const float* pred, const float* target, long long nplanes,
+                        int H, int W, float weight, const float* ssim4, float* dy, hipStream_t st);
 int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
 int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
                                hipStream_t st);

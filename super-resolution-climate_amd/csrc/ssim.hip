@@ -46,50 +46,17 @@
 
 #include "common.hpp"
 #include "srmi_internal.hpp"
+#include "ssim_common.hpp"  // the window, the tile shape, the taps and the two passes: shared with ssim_loss.hip
 
 namespace srmi {
 
 namespace {
 
-constexpr int kSsimThreads = 256;
-constexpr int kSsimR = 5, kSsimTaps = 2 * kSsimR + 1;
-constexpr int kTileH = 24, kTileW = 64;              // output pixels of a workgroup
-constexpr int kHaloH = kTileH + 2 * kSsimR;          // 34 staged rows
-constexpr int kHaloW = kTileW + 2 * kSsimR;          // 74 staged columns
-constexpr int kRowsPerThread = kTileH / (kSsimThreads / kTileW);  // 6: a thread owns 6 rows of one column
-constexpr int kMmBlocks = 512;                       // min / max workgroups per channel, at most
-constexpr int kMmPerThread = 16;                     // pixels per thread at which the min / max grid stops growing
-static_assert(kSsimThreads % kTileW == 0 && kTileH % (kSsimThreads / kTileW) == 0, "tile does not fit the workgroup");
-
-struct SsimTaps {
-  float g[kSsimTaps];
-};
-
-__device__ inline bool ssim_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
 __global__ void __launch_bounds__(kSsimThreads) ssim_minmax_kernel(const float* __restrict__ b, long long HW,
                                                                    int nblk, float* __restrict__ mm) {
   __shared__ float slo[kSsimThreads], shi[kSsimThreads];
   const int c = blockIdx.y, tid = threadIdx.x;
-  const float* p = b + (size_t)c * (size_t)HW;
-  const float nan = __uint_as_float(0x7fc00000u);
-  float lo = nan, hi = nan;
-  for (long long i = (long long)blockIdx.x * kSsimThreads + tid; i < HW; i += (long long)nblk * kSsimThreads) {
-    float v = p[i];
-    v = ssim_nonfinite(v) ? nan : v;
-    lo = fminf(lo, v);  // minNum: a NaN operand is ignored
-    hi = fmaxf(hi, v);
-  }
-  slo[tid] = lo;
-  shi[tid] = hi;
-  __syncthreads();
-  for (int o = kSsimThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      slo[tid] = fminf(slo[tid], slo[tid + o]);
-      shi[tid] = fmaxf(shi[tid], shi[tid + o]);
-    }
-    __syncthreads();
-  }
+  ssim_minmax_block(b + (size_t)c * (size_t)HW, HW, blockIdx.x, nblk, slo, shi, tid);
   if (tid == 0) {
     mm[((size_t)c * nblk + blockIdx.x) * 2 + 0] = slo[0];
     mm[((size_t)c * nblk + blockIdx.x) * 2 + 1] = shi[0];
@@ -120,23 +87,7 @@ __global__ void __launch_bounds__(kSsimThreads, 2) ssim_tile_kernel(const float*
   const float nan = __uint_as_float(0x7fc00000u);
 
   // ---- r and L of the channel: min / max do not depend on the order
-  {
-    float lo = nan, hi = nan;
-    for (int i = tid; i < nblk; i += kSsimThreads) {
-      lo = fminf(lo, mm[((size_t)c * nblk + i) * 2 + 0]);
-      hi = fmaxf(hi, mm[((size_t)c * nblk + i) * 2 + 1]);
-    }
-    slo[tid] = lo;
-    shi[tid] = hi;
-    __syncthreads();
-    for (int o = kSsimThreads / 2; o > 0; o >>= 1) {
-      if (tid < o) {
-        slo[tid] = fminf(slo[tid], slo[tid + o]);
-        shi[tid] = fmaxf(shi[tid], shi[tid + o]);
-      }
-      __syncthreads();
-    }
-  }
+  ssim_minmax_fold(mm + (size_t)c * nblk * 2, nblk, slo, shi, tid);
   const float lo = slo[0], hi = shi[0];
   const float r = 0.5f * lo + 0.5f * hi;  // halving is exact: one rounding, no overflow
   const float L = data_range > 0.0f ? data_range : hi - lo;
@@ -169,56 +120,13 @@ __global__ void __launch_bounds__(kSsimThreads, 2) ssim_tile_kernel(const float*
   __syncthreads();
 
   // ---- horizontal pass: one thread per (staged row, output column), taps in ascending order
-  for (int e = tid; e < kHaloH * kTileW; e += kSsimThreads) {
-    const int ly = e / kTileW, lx = e % kTileW;
-    const float* pa = sa + ly * kHaloW + lx;
-    const float* pb = sb + ly * kHaloW + lx;
-    float ma = 0.0f, mb = 0.0f, aa = 0.0f, bb = 0.0f, ab = 0.0f, cnt = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kSsimTaps; ++k) {
-      float va = pa[k];
-      const float vb = pb[k];
-      const bool bad = va != va;
-      cnt += bad ? 1.0f : 0.0f;
-      va = bad ? 0.0f : va;
-      const float g = taps.g[k];
-      ma = fmaf(g, va, ma);
-      mb = fmaf(g, vb, mb);
-      aa = fmaf(g, va * va, aa);
-      bb = fmaf(g, vb * vb, bb);
-      ab = fmaf(g, va * vb, ab);
-    }
-    hp[0][e] = ma;
-    hp[1][e] = mb;
-    hp[2][e] = aa;
-    hp[3][e] = bb;
-    hp[4][e] = ab;
-    hp[5][e] = cnt;
-  }
+  ssim_horizontal_pass(sa, sb, hp, taps, tid);
   __syncthreads();
 
   // ---- vertical pass: a thread owns kRowsPerThread consecutive rows of one column
   const int lx = tid % kTileW, ry = (tid / kTileW) * kRowsPerThread;
   float acc[kRowsPerThread][6];
-#pragma unroll
-  for (int i = 0; i < kRowsPerThread; ++i)
-#pragma unroll
-    for (int q = 0; q < 6; ++q) acc[i][q] = 0.0f;
-#pragma unroll
-  for (int j = 0; j < kRowsPerThread + kSsimTaps - 1; ++j) {
-    float v[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) v[q] = hp[q][(ry + j) * kTileW + lx];
-#pragma unroll
-    for (int i = 0; i < kRowsPerThread; ++i) {
-      const int k = j - i;  // output row i reads staged rows i .. i + 10, ascending
-      if (k >= 0 && k < kSsimTaps) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) acc[i][q] = fmaf(taps.g[k], v[q], acc[i][q]);
-        acc[i][5] += v[5];
-      }
-    }
-  }
+  ssim_vertical_pass(hp, taps, lx, ry, acc);
   const float k1 = 0.01f * L, k2 = 0.03f * L;
   const float C1 = k1 * k1, C2 = k2 * k2;
   double s_ssim = 0.0, s_cs = 0.0;
@@ -356,14 +264,7 @@ int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_
   float* mm = reinterpret_cast<float*>(base + p.off_mm);
   float* lout = reinterpret_cast<float*>(base + p.off_l);
   SsimTaps taps;
-  {  // normalised in fp64, then rounded
-    double g[kSsimTaps], s = 0.0;
-    for (int k = 0; k < kSsimTaps; ++k) {
-      g[k] = exp(-(double)((k - kSsimR) * (k - kSsimR)) / (2.0 * 1.5 * 1.5));
-      s += g[k];
-    }
-    for (int k = 0; k < kSsimTaps; ++k) taps.g[k] = (float)(g[k] / s);
-  }
+  ssim_fill_taps(&taps);
   hipLaunchKernelGGL(ssim_minmax_kernel, dim3(p.nblk, C), dim3(kSsimThreads), 0, st, b, (long long)H * W, p.nblk, mm);
   SRMI_CHECK_LAUNCH();
   hipLaunchKernelGGL(ssim_tile_kernel, dim3((unsigned)p.ntiles), dim3(kSsimThreads), 0, st, a, b, H, W, p.tiles_x,

@@ -171,6 +171,10 @@ _SIGS = {
     "srmi_consistency_adjoint_apply": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
     "srmi_ssim_workspace":([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_ssim": ([P, P, C.c_int, C.c_int, C.c_int, C.c_float, P, C.c_size_t, P, P, P, P], C.c_int),
+    "srmi_ssim_loss_workspace": ([C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_ssim_loss_parts": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, P, P, P, C.c_size_t, P], C.c_int),
+    "srmi_ssim_loss_from_parts": ([P, P, C.c_longlong, C.c_float, P, P, P, P], C.c_int),
+    "srmi_ssim_loss_dy": ([P, C.c_size_t, P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, P, P, P], C.c_int),
     "srmi_distribution_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_distribution": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F, C.POINTER(C.c_double), C.c_int, P,
                            C.c_size_t, P, P, P, P, P, C.c_int, P], C.c_int),

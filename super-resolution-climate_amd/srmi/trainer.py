@@ -32,6 +32,7 @@ from .engine import (Engine, NetSpec, adam_step, adam_step_guarded, axpy, downsa
 from .consistency import ConsistencyLayer
 from .optim import check_clip_norm, check_ema, check_guard, ema_decay_at, make_lr_schedule
 from .spectra import SpectralLoss, check_spectral_loss_config
+from .ssim import SSIM_WINDOW, SSIMLoss, check_ssim_loss_config
 from .superres import check_consistent
 
 LOSS_KINDS = {"l2": SRMI_LOSS_RMSE, "charbonnier": SRMI_LOSS_MEAN}
@@ -78,7 +79,7 @@ class FusedTrainer:
                  cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
                  land: bool = False, spectral: Optional[Mapping] = None, consistent: int = 0,
                  clip_norm: Optional[float] = None, guard: Optional[bool] = None, ema: Optional[Mapping] = None,
-                 lr_schedule=None):
+                 lr_schedule=None, ssim: Optional[Mapping] = None):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -108,6 +109,15 @@ class FusedTrainer:
         the sum of both upstream gradients.  Windows that touch a non-finite pixel are
         skipped, so land=True needs nothing more.  A bad window, stride, weight (finite,
         >= 0) or eps raises ValueError here.
+        ssim (no reference counterpart; DESIGN.md §1 "SSIM loss"): None, or the configuration
+        of an SSIM loss term, dict(weight=1.0, data_range=None) (srmi.ssim.SSIMLoss's
+        arguments; a missing key takes that default).  The step's loss is then loss_fn (+
+        the spectral term) + weight * L_ssim, L_ssim = 1 - the mean of SSIMScore's ssim over
+        the used positions of the global batch (data_range None: every target plane's own
+        range), and its gradient is added to the upstream gradient after the spectral term's.
+        Positions whose window touches a non-finite pixel are not used, so land=True needs
+        nothing more.  Unknown keys, a bad weight (finite, >= 0) or range, or an HR tile below
+        11 pixels (the window) in either dimension raise ValueError here.
         consistent (no reference counterpart; DESIGN.md §1 "Consistency in training"): K in
         0 .. 16.  K > 0 makes K steps of back-projection onto the LR input the model's last,
         parameter-free layer (srmi.consistency.ConsistencyLayer): the network's output is
@@ -189,6 +199,18 @@ class FusedTrainer:
                 raise ValueError(f"spectral loss window {P} larger than the HR tile "
                                  f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
             spectral_cfg = dict(window=P, stride=Q, eps=seps, weight=sw)
+        ssim_cfg = None
+        if ssim is not None:
+            if not isinstance(ssim, Mapping):
+                raise ValueError(f"ssim: a dict(weight=, data_range=) or None, got {ssim!r}")
+            extra = set(ssim) - {"weight", "data_range"}
+            if extra:
+                raise ValueError(f"ssim: unknown keys {sorted(extra)}")
+            sw, sdr = check_ssim_loss_config(ssim.get("weight", 1.0), ssim.get("data_range"))
+            if min(lr_hw) * spec.scale < SSIM_WINDOW:
+                raise ValueError(f"ssim loss window {SSIM_WINDOW} larger than the HR tile "
+                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
+            ssim_cfg = dict(weight=sw, data_range=sdr)
         self.info = info or DistInfo()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.tindx = None if tindx is None else torch.tensor(tindx, dtype=torch.long, device=self.device)
@@ -234,10 +256,11 @@ class FusedTrainer:
                    if interp_loss else None)
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
         # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
-        # (a spectral term: always -- its gradient is added to the pixel loss's)
+        # (a spectral or an SSIM term: always -- its gradient is added to the pixel loss's)
         # (a consistency layer: always -- its adjoint runs on it)
         self.dy = (torch.empty_like(self.sr)
-                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None or self.consistent
+                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None
+                   or ssim_cfg is not None or self.consistent
                    else None)
         # the consistency layer and, with land, the LR batch as it was before the flood fill
         self.layer = (ConsistencyLayer((batch, C, h, w), s, self.umode, self.dmode, self.consistent, self.device)
@@ -269,6 +292,10 @@ class FusedTrainer:
         # parts and used-window counts of the GLOBAL batch, which travel as gparts does
         self.spectral = (SpectralLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **spectral_cfg)
                          if spectral_cfg is not None else None)
+        # the SSIM term: the coefficient maps of this rank's tiles, and the per-plane sums and
+        # used-position counts of the GLOBAL batch, which travel as the spectral term's do
+        self.ssim = (SSIMLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **ssim_cfg)
+                     if ssim_cfg is not None else None)
         self.streams = [None] + [engine_stream(self.device) for _ in range(micro - 1)]
         self.dp_staged = not dp_reducer_stream
         self.reducer = GradReducer(self.eng.table, spec.arch, spec.nlayers, self.info, self.device,
@@ -384,6 +411,11 @@ class FusedTrainer:
             if self.info.enabled:
                 for v in self.spectral.views():
                     v.zero_()
+        if self.ssim is not None:
+            self.ssim.set_global_batch(gb)
+            if self.info.enabled:
+                for v in self.ssim.views():
+                    v.zero_()
         for st in self.streams[1:]:
             st.wait_stream(main)
         # forward + loss partials per micro-batch (an empty micro-batch adds nothing)
@@ -408,6 +440,8 @@ class FusedTrainer:
                 self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start, lcparts)
                 if self.spectral is not None:
                     self.spectral.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
+                if self.ssim is not None:
+                    self.ssim.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
                 if self.interp_loss:  # self.loss(btarget, binterp), dual_trainer.py:316-317
                     up = upsample(self.lrbuf[sl], s, out=self.up[sl], mode=self.umode)
                     itgt = hr[sl] if self.tgt_b is None else self.tgt_b[sl]
@@ -419,12 +453,16 @@ class FusedTrainer:
             if self.info.enabled:
                 allreduce_sum_(self.spectral.gparts[:2 * gb * self.spectral.C], self.info)
             self.spectral.finalize(self.loss4)
+        if self.ssim is not None:  # chained: its total is the pixel loss (+ the spectral term) + its own
+            if self.info.enabled:
+                allreduce_sum_(self.ssim.gparts[:2 * gb * self.ssim.C], self.info)
+            self.ssim.finalize(self.loss4[3:4] if self.spectral is None else self.spectral.total)
         for st in self.streams[1:]:
             st.wait_stream(main)
-        # the upstream gradient from the finalised loss, zero on land; with a spectral term
+        # the upstream gradient from the finalised loss, zero on land; with a spectral or SSIM term
         # or a consistency layer the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then
-        # the term's on top
-        explicit = self.spectral is not None or self.layer is not None
+        # the terms' on top
+        explicit = self.spectral is not None or self.ssim is not None or self.layer is not None
         if self.land or (explicit and self.loss_kind == SRMI_LOSS_RMSE):
             for k in range(self.micro):
                 sl = sls[k]
@@ -439,6 +477,12 @@ class FusedTrainer:
                 if sl.stop > sl.start:
                     with self._ctx(k):
                         self.spectral.add_dy(self.dy[sl], rows=sl.start)
+        if self.ssim is not None:
+            for k in range(self.micro):
+                sl = sls[k]
+                if sl.stop > sl.start:
+                    with self._ctx(k):
+                        self.ssim.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
         if self.layer is not None:  # through the layer's adjoint: dy becomes the network output's gradient
             for k in range(self.micro):
                 sl = sls[k]
@@ -536,6 +580,8 @@ class FusedTrainer:
                    "spectral_loss": self.spectral.spec4[3:4]}
         else:
             out = {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
+        if self.ssim is not None:
+            out.update(loss=self.ssim.total, pixel_loss=self.loss4[3:4], ssim_loss=self.ssim.ssim4[3:4])
         if self.guard:
             out["grad_norm"] = self.ctl[0:1]
             out["step_skipped"] = self.ctl[2:3]
