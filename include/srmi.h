@@ -78,6 +78,14 @@
  *                                   Wasserstein-1 distance and quantiles formed from them.
  *                                   No reference counterpart: the reference scores a field
  *                                   by its RMSE alone.
+ *   srmi_quantile_map_accumulate_workspace,
+ *   srmi_quantile_map_accumulate,
+ *   srmi_quantile_map_fit,
+ *   srmi_quantile_map_apply      -> empirical quantile mapping of a super-resolved field: the
+ *                                   histograms of output and truth accumulated over a
+ *                                   calibration set, the monotone transfer table built from
+ *                                   them, and the field mapped through it.  No reference
+ *                                   counterpart: the reference never calibrates its output.
  *   srmi_spectral_loss_workspace,
  *   srmi_spectral_loss_parts,
  *   srmi_spectral_loss_from_parts,
@@ -780,6 +788,76 @@ int srmi_distribution_workspace(int C, int H, int W, int nbins, int njoint, size
 int srmi_distribution(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
                       const double* probs, int nprobs, void* workspace, size_t workspace_bytes, long long* hist,
                       long long* joint, float* range, long long* count, double* derived, int flags, void* stream);
+
+/* ---- quantile mapping (no reference counterpart) ------------------------- */
+/* Empirical quantile mapping: a monotone transfer function T = F_truth^-1 o F_src, calibrated
+ * on fields whose truth is known and applied to later ones, so that the mapped output has the
+ * truth's distribution of values (or of detail, value minus an interpolated base).
+ * tests/quantile_map_oracle.py restates the three entry points in numpy.  Shared conventions:
+ * B = nbins in 2 .. 4096, M = B + 2 entries {under, B bins, over}, C in 1 .. 16; `range` is a
+ * HOST array [C][2] of finite fp32 {lo, hi} with hi > lo and hi - lo finite in fp32, one pair per
+ * channel (the fixed range is what lets the tables of many fields add); H, W >= 1 with H W <= 2^31 - 1.  An argument
+ * outside this: SRMI_ERR_ARG, nothing is launched and every output is left as it was.  No
+ * global atomics, no host synchronisation, no allocation: all three are capturable.  No
+ * reference counterpart.
+ *
+ * srmi_quantile_map_accumulate: src, truth, base [C][H][W] fp32 on the device, base may be
+ * NULL.  The binned values are src - base and truth - base (one fp32 subtraction each,
+ * rounded once), or src and truth without base.  A pixel is used iff both binned values are
+ * finite.  The bin is srmi_distribution's, exactly: scale = fp32(B) / (hi - lo), entry 0 below
+ * lo, entry B + 1 above hi, x == hi in entry B, the comparisons before any conversion.  hist
+ * [C][2][B + 2] int64 (0: src, 1: truth), count [C] int64 = the used pixels.  first != 0
+ * overwrites hist and count, first == 0 adds to them.  Launches: histogram partials (LDS
+ * integer atomics, one int32 table per workgroup, plain stores), then finish, the single
+ * writer of every entry, which reads the partial tables in workgroup order: exact and
+ * bit-identical from run to run.  srmi_quantile_map_accumulate_workspace (host only) gives the
+ * bytes of `workspace` (16-byte aligned; it need not be initialised).  No alignment
+ * requirement on src, truth or base.  A missing src, truth, workspace, hist, count or range, a
+ * workspace that is too small or not aligned, B, C or a range outside the above, H or W < 1
+ * or H W > 2^31 - 1: SRMI_ERR_ARG.
+ *
+ * srmi_quantile_map_fit: one launch, one workgroup per channel, from the int64 tables alone
+ * (count is what accumulate wrote beside them; N below is the tables' own sum, which equals
+ * it).  With w = (hi - lo) / B in fp64 and edge[j] = lo + (j - 1) w for j = 0 .. M, edge[B + 1]
+ * = hi exactly: ca[j], cb[j] = the cumulative counts of the src and truth tables before entry
+ * j (ca[0] = 0, ca[M] = N).  T[j] = F_truth^-1(ca[j]) by the score's piecewise-linear
+ * quantile: if cb[k] < ca[j] < cb[k + 1] for some k, T[j] = edge[k] + w (ca[j] - cb[k]) /
+ * hb[k]; the search is over integers, only that line is fp64 arithmetic.  Tie rule (minimal
+ * displacement): if ca[j] == cb[k] for k in k0 .. k1 (empty truth bins), the quantile is any
+ * point of [edge[k0], edge[k1]], the left end -Inf when ca[j] == 0 and the right end +Inf
+ * when ca[j] == N; T[j] is the point nearest to edge[j], clamp(edge[j], left, right).  Equal
+ * tables therefore give T = edge, and T is non-decreasing for any pair of tables.  Tails:
+ * tail_count >= 0; a knot with ca[j] < tail_count or N - ca[j] < tail_count is not trusted;
+ * with j0, j1 the first and last trusted knots, the knots below j0 are edge[j] + (T[j0] -
+ * edge[j0]) and those above j1 edge[j] + (T[j1] - edge[j1]), the constant-shift extrapolation
+ * of quantile-mapping practice; no trusted knot, or N == 0: T = edge, the identity.  knots
+ * [C][M + 1] fp64 = T; table [C][M + 1] fp32 = fp32(T); meta [C][4] fp32 = {lo, hi, fp32(T[0] -
+ * edge[0]), fp32(T[M] - edge[M])}.  A missing hist, count, range, knots, table or meta, B, C
+ * or a range outside the above, tail_count < 0: SRMI_ERR_ARG.
+ *
+ * srmi_quantile_map_apply: x, base, out [C][H][W] fp32 on the device; out may be x (in place)
+ * and must otherwise not overlap it; base may be NULL and must not overlap out.  table and
+ * meta are fit's, on the device.  Per pixel, every operation fp32 and rounded once, none
+ * fused, with scale = fp32(B) / (hi - lo):
+ *   v = x - base (x without base); v NaN: out = x, the same bits;
+ *   u = (v - lo) * scale + 1; u < 0: out = x + strength * meta[2]; u >= M: out = x + strength
+ *   * meta[3] (decided before any conversion: +-Inf and huge values index nothing);
+ *   otherwise k = min((int)u, M - 1), f = u - (float)k, y = table[k] + f * (table[k + 1] -
+ *   table[k]), out = x + strength * (y - v).
+ * The correction is added to x in both modes: base only locates v.  strength finite in [0, 1].
+ * One launch: the channel's table as (value, slope) pairs in LDS, one 8-byte LDS read per
+ * pixel; 16-byte global accesses where x, base and out of a plane are 16-byte aligned, scalar
+ * ones where not.  A missing x, table, meta or out, out overlapping base or partly
+ * overlapping x, strength outside [0, 1] (NaN included), B or C outside the above, H or W < 1
+ * or H W > 2^31 - 1: SRMI_ERR_ARG. */
+int srmi_quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes);
+int srmi_quantile_map_accumulate(const float* src, const float* truth, const float* base, int C, int H, int W,
+                                 int nbins, const float* range, int first, void* workspace, size_t workspace_bytes,
+                                 long long* hist, long long* count, void* stream);
+int srmi_quantile_map_fit(const long long* hist, const long long* count, int C, int nbins, const float* range,
+                          long long tail_count, double* knots, float* table, float* meta, void* stream);
+int srmi_quantile_map_apply(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
+                            const float* meta, float strength, float* out, void* stream);
 
 /* ---- consistency with the coarse input (no reference counterpart) -------- */
 /* Iterative back-projection x <- x + U(lr - D x) of an HR field x [C][h s][w s] onto the LR

@@ -42,6 +42,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "dist_bin.hpp"
 #include "srmi_internal.hpp"
 
 // (x - lo) * scale and the fp64 forms below are the defined operations: no fused forms
@@ -52,7 +53,6 @@ namespace srmi {
 namespace {
 
 constexpr int kDistThreads = 1024;                  // histogram and finish workgroups
-constexpr int kDistRun = 8;                         // consecutive pixels of a lane per step
 constexpr int kDistSpan = kDistThreads * kDistRun;  // 8192 pixels of a workgroup per step
 constexpr int kDistBlocks = 256;                    // histogram workgroups per channel, at most
 constexpr int kRangeThreads = 256;
@@ -68,28 +68,6 @@ static_assert(kRangeBlocks <= kDistThreads, "the fold reads one pair per thread"
 struct DistProbs {
   double p[kDistMaxProbs];
 };
-
-__device__ inline bool dist_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// 8 consecutive pixels from i0 (a multiple of 8); past the plane: NaN, which no one uses.
-// vec: the plane starts on a 16-byte boundary.
-__device__ inline void dist_load_run(const float* __restrict__ p, long long i0, long long HW, bool vec,
-                                     float (&v)[kDistRun]) {
-  if (i0 + kDistRun <= HW) {
-    if (vec) {
-      const float4 q0 = *reinterpret_cast<const float4*>(p + i0);
-      const float4 q1 = *reinterpret_cast<const float4*>(p + i0 + 4);
-      v[0] = q0.x, v[1] = q0.y, v[2] = q0.z, v[3] = q0.w;
-      v[4] = q1.x, v[5] = q1.y, v[6] = q1.z, v[7] = q1.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kDistRun; ++k) v[k] = p[i0 + k];
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kDistRun; ++k) v[k] = i0 + k < HW ? p[i0 + k] : __uint_as_float(0x7fc00000u);
-  }
-}
 
 __global__ void __launch_bounds__(kRangeThreads) dist_range_kernel(const float* __restrict__ a,
                                                                    const float* __restrict__ b, long long HW,
@@ -127,16 +105,6 @@ __global__ void __launch_bounds__(kRangeThreads) dist_range_kernel(const float* 
     mm[(size_t)blockIdx.x * 2 + 0] = slo[0];
     mm[(size_t)blockIdx.x * 2 + 1] = shi[0];
   }
-}
-
-// index into the n + 2 entries {under, n bins, over}.  The comparisons decide under and over
-// before any conversion, and the converted value is clamped again as an integer.
-__device__ inline int dist_bin(float x, float lo, float hi, float scale, int n) {
-  if (x < lo) return 0;
-  if (x > hi) return n + 1;
-  if (x == hi) return n;  // what the formula gives whenever hi > lo; also the bin when hi == lo
-  const int k = (int)__fmul_rn(__fsub_rn(x, lo), scale);
-  return 1 + min(max(k, 0), n - 1);
 }
 
 // one table's counts of a lane's run: equal neighbours once (Merge) or every pixel for itself

@@ -1692,6 +1692,27 @@ int srmi_distribution(const float* a, const float* b, int C, int H, int W, int n
                              joint, range, count, derived, flags, S_(stream));
 }
 
+int srmi_quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes) {
+  return quantile_map_accumulate_workspace(C, H, W, nbins, bytes);
+}
+
+int srmi_quantile_map_accumulate(const float* src, const float* truth, const float* base, int C, int H, int W,
+                                 int nbins, const float* range, int first, void* workspace, size_t workspace_bytes,
+                                 long long* hist, long long* count, void* stream) {
+  return quantile_map_accumulate_launch(src, truth, base, C, H, W, nbins, range, first, workspace, workspace_bytes,
+                                        hist, count, S_(stream));
+}
+
+int srmi_quantile_map_fit(const long long* hist, const long long* count, int C, int nbins, const float* range,
+                          long long tail_count, double* knots, float* table, float* meta, void* stream) {
+  return quantile_map_fit_launch(hist, count, C, nbins, range, tail_count, knots, table, meta, S_(stream));
+}
+
+int srmi_quantile_map_apply(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
+                            const float* meta, float strength, float* out, void* stream) {
+  return quantile_map_apply_launch(x, base, C, H, W, nbins, table, meta, strength, out, S_(stream));
+}
+
 int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
   return spectral_loss_workspace(nplanes, H, W, P, Q, bytes);
 }

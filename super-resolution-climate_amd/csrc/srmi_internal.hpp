@@ -342,6 +342,15 @@ int distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* b
 int distribution_launch(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
                         const double* probs, int nprobs, void* ws, size_t ws_bytes, long long* hist, long long* joint,
                         float* range, long long* count, double* derived, int flags, hipStream_t st);
+// the quantile map: accumulated histograms, the transfer table, the mapped field (quantile_map.hip)
+int quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes);
+int quantile_map_accumulate_launch(const float* src, const float* truth, const float* base, int C, int H, int W,
+                                   int nbins, const float* range, int first, void* ws, size_t ws_bytes,
+                                   long long* hist, long long* count, hipStream_t st);
+int quantile_map_fit_launch(const long long* hist, const long long* count, int C, int nbins, const float* range,
+                            long long tail_count, double* knots, float* table, float* meta, hipStream_t st);
+int quantile_map_apply_launch(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
+                              const float* meta, float strength, float* out, hipStream_t st);
 // the spectral loss term of the training step (spectral_loss.hip)
 int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
 int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,

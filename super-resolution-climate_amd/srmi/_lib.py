@@ -178,6 +178,11 @@ _SIGS = {
     "srmi_distribution_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_distribution": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F, C.POINTER(C.c_double), C.c_int, P,
                            C.c_size_t, P, P, P, P, P, C.c_int, P], C.c_int),
+    "srmi_quantile_map_accumulate_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_quantile_map_accumulate": ([P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, F, C.c_int, P, C.c_size_t, P, P, P],
+                                     C.c_int),
+    "srmi_quantile_map_fit": ([P, P, C.c_int, C.c_int, F, C.c_longlong, P, P, P, P], C.c_int),
+    "srmi_quantile_map_apply": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

@@ -434,6 +434,82 @@ def load_distribution(path: str) -> Tuple[Dict[str, np.ndarray], List[str], np.n
         return out, names.split(",") if names else [], pr
 
 
+def save_quantile_map(path: str, qmap, varnames: Sequence[str]) -> str:
+    """One quantile map (srmi.quantile_map.QuantileMap, or its ``state_dict()``) as a netCDF-3
+    file, through the same scipy writer.  The integer tables -- 'hist_src', 'hist_truth' on
+    ('channel', 'entry'), 'count' on ('channel',) -- are float64 as save_distribution's are
+    (netCDF-3 has no int64; a double holds every count below 2^53 exactly, and a larger one
+    is refused).  'lo', 'hi' float32 on ('channel',); 'edges' float64 on ('channel', 'edge'),
+    the B + 3 positions of the knots (srmi.distribution.bin_edges); 'knots' float64 on
+    ('channel', 'edge') when the map was fitted.  Attributes: ``varnames`` (the channel names
+    joined by ``,``), ``bins``, ``on``, ``tail_count``.  The table itself is not stored:
+    load_state_dict re-derives it from the integer tables.  No reference counterpart."""
+    from scipy.io import netcdf_file
+
+    from .distribution import bin_edges
+    sd = qmap.state_dict() if hasattr(qmap, "state_dict") else qmap
+    missing = [k for k in ("hist", "count", "range", "bins", "on", "tail_count") if k not in sd]
+    if missing:
+        raise ValueError(f"the quantile map's state lacks {missing}")
+    n, B = len(varnames), int(sd["bins"])
+    hist = np.ascontiguousarray(_np(sd["hist"]).astype(np.int64))
+    count = np.ascontiguousarray(_np(sd["count"]).astype(np.int64))
+    rng = np.ascontiguousarray(_np(sd["range"]).astype(np.float32))
+    for q, a, shape in (("hist", hist, (n, 2, B + 2)), ("count", count, (n,)), ("range", rng, (n, 2))):
+        if a.shape != shape:
+            raise ValueError(f"{q}: {a.shape} is not {shape}")
+    if hist.size and int(hist.max()) >= 2 ** 53 or int(count.max()) >= 2 ** 53:
+        raise ValueError("a count of 2^53 or more does not fit a double")
+    if sd["on"] not in ("detail", "value"):
+        raise ValueError(f"on {sd['on']!r}")
+    knots = None
+    if sd.get("knots") is not None:
+        knots = np.ascontiguousarray(_np(sd["knots"]).astype(np.float64))
+        if knots.shape != (n, B + 3):
+            raise ValueError(f"knots: {knots.shape} is not {(n, B + 3)}")
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        f.bins = np.int32(B)
+        f.on = str(sd["on"])
+        f.tail_count = np.float64(int(sd["tail_count"]))
+        f.createDimension("channel", n)
+        f.createDimension("entry", B + 2)
+        f.createDimension("edge", B + 3)
+        for k, q in enumerate(("hist_src", "hist_truth")):
+            dv = f.createVariable(q, np.float64, ("channel", "entry"))
+            dv[:] = hist[:, k].astype(np.float64)
+        dv = f.createVariable("count", np.float64, ("channel",))
+        dv[:] = count.astype(np.float64)
+        for k, q in enumerate(("lo", "hi")):
+            dv = f.createVariable(q, np.float32, ("channel",))
+            dv[:] = rng[:, k]
+        ev = f.createVariable("edges", np.float64, ("channel", "edge"))
+        ev[:] = bin_edges(rng[:, 0], rng[:, 1], B)
+        if knots is not None:
+            kv = f.createVariable("knots", np.float64, ("channel", "edge"))
+            kv[:] = knots
+    return path
+
+
+def load_quantile_map(path: str) -> Tuple[Dict[str, object], List[str]]:
+    """The inverse of save_quantile_map: (the state QuantileMap.load_state_dict takes, the
+    counts int64 again, with 'edges' and, where stored, 'knots' beside them; varnames)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        on = f.on.decode() if isinstance(f.on, bytes) else str(f.on)
+        hist = np.stack([np.array(f.variables[q][:]).astype(np.int64) for q in ("hist_src", "hist_truth")], 1)
+        sd = {"hist": hist, "count": np.array(f.variables["count"][:]).astype(np.int64),
+              "range": np.stack([np.array(f.variables[q][:], dtype=np.float32) for q in ("lo", "hi")], 1),
+              "bins": int(f.bins), "on": on, "tail_count": int(f.tail_count),
+              "edges": np.array(f.variables["edges"][:], dtype=np.float64)}
+        if "knots" in f.variables:
+            sd["knots"] = np.array(f.variables["knots"][:], dtype=np.float64)
+        return sd, names.split(",") if names else []
+
+
 def load_spectra(path: str) -> Tuple[Dict[str, np.ndarray], int, List[str]]:
     """The inverse of save_spectra: (spectra as numpy arrays, window, varnames)."""
     from scipy.io import netcdf_file

@@ -91,6 +91,20 @@ its input is finite and every tap of D in 'model' is; the others have a zero res
 every step, and a non-finite pixel of 'model' is never written, so with ``land=True`` and
 bad tiles the NaN set and bits of 'model' are what they were.  'interpolated' and 'spread'
 are untouched; ``score`` and ``score_spectra`` score the corrected field.
+
+Quantile mapping (``quantile_map=QuantileMap``)
+-----------------------------------------------
+An RMSE-trained network pulls its output to the mean and under-fills the tails
+(``score_distribution``'s 'q_bias').  With a fitted srmi.quantile_map.QuantileMap, 'model' is
+mapped in place through its transfer table (``srmi_quantile_map_apply``): x <- x + qm_strength
+(T(v) - v), with v = x - 'interpolated' for a map on="detail" and v = x for on="value".  The
+order is fixed: AFTER the blend (the ensemble's included, so the mean is mapped, and 'spread'
+is what it is without) and BEFORE the consistency correction, so ``consistent=K`` re-imposes
+the coarse constraint on the mapped field -- the map moves values, the back-projection
+restores what it moved at the coarse scale.  A NaN pixel is written back as it was, so
+``land=True`` needs nothing more.  ``fit_quantile_map`` calibrates a map on regions whose
+truth is known.  Out of scope: srmi.inference.TiledInference, training through the map, and a
+map that varies in space or with the season.
 """
 from __future__ import annotations
 
@@ -200,7 +214,7 @@ class RegionSuperResolver:
                  tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
                  task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
                  device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25, ensemble=1,
-                 consistent: int = 0):
+                 consistent: int = 0, quantile_map=None, qm_strength: float = 1.0):
         """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
         runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
         overlap).
@@ -247,7 +261,17 @@ class RegionSuperResolver:
         consistent: an integer 0 .. 16, the steps of back-projection applied to 'model'
         (see the module docstring).  It needs an even scale, >= 4 when the task's
         downsample is bicubic: ValueError otherwise.  consistent=0 is the object as it
-        was, bit for bit."""
+        was, bit for bit.
+
+        quantile_map: a fitted srmi.quantile_map.QuantileMap of C channels on this device,
+        applied to 'model' with qm_strength in [0, 1] (see the module docstring); ValueError
+        for another channel count or device, an unfitted map or a strength outside [0, 1].
+        The apply sits inside the captured graph (graph=True), which reads the map's device
+        buffers: a refit of the SAME object (accumulate, fit, load_state_dict) takes effect at
+        the next replay, with no recapture -- as long as the map's ``on`` stays what it was,
+        because whether the base is passed is part of the captured launch; qm_strength and
+        ``on`` are fixed at construction (a state of another ``on`` needs a new resolver).
+        quantile_map=None is the object as it was, bit for bit."""
         if task is None:  # the active srmi ConfigContext's task section, if any
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
@@ -264,6 +288,20 @@ class RegionSuperResolver:
         self.consistent = check_consistent(consistent, spec.scale, self.dmode, self.umode)
         self.spec = spec
         self.device = device or params.device
+        self.quantile_map, self.qm_strength = quantile_map, float(qm_strength)
+        self._qm_on = None if quantile_map is None else quantile_map.on
+        if quantile_map is not None:
+            dv = torch.device(self.device)
+            if dv.type == "cuda" and dv.index is None:
+                dv = torch.device("cuda", torch.cuda.current_device())
+            if quantile_map.C != int(region_chw_lr[0]):
+                raise ValueError(f"quantile_map holds {quantile_map.C} channels, the region has {int(region_chw_lr[0])}")
+            if quantile_map.device != dv:
+                raise ValueError(f"quantile_map lives on {quantile_map.device}, the resolver on {dv}")
+            if not quantile_map.fitted:
+                raise ValueError("quantile_map has no table yet: fit() or load_state_dict() it first")
+            if not (math.isfinite(self.qm_strength) and 0.0 <= self.qm_strength <= 1.0):
+                raise ValueError(f"qm_strength {qm_strength!r}: a number in [0, 1]")
         C, h, w = (int(v) for v in region_chw_lr)
         if C != spec.nchannels_in or spec.nchannels_in != spec.nchannels_out:
             raise ValueError("region channels must equal the model's input/output channels")
@@ -404,7 +442,7 @@ class RegionSuperResolver:
         call("srmi_tiles_blend", ptr(self.sr), ptr(self.off), ptr(self.div), ptr(self.bad), self.C, self.ty * s,
              self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.images["model"]), stream_handle())
 
-    def _run(self):
+    def _run(self, use_map: bool = True, correct: bool = True):
         self._cut()
         if self.K > 1:
             self._expand()
@@ -415,7 +453,13 @@ class RegionSuperResolver:
         else:
             upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
         self._blend()
-        if self.consistent:
+        if use_map and self.quantile_map is not None:
+            qm, model = self.quantile_map, self.images["model"]
+            if qm.on != self._qm_on:
+                raise ValueError(f"quantile_map was on={self._qm_on!r} when this resolver was built and is "
+                                 f"on={qm.on!r} now: build a new resolver")
+            qm.apply(model, self.images["interpolated"] if qm.on == "detail" else None, self.qm_strength, out=model)
+        if self.consistent and correct:
             self._correct()
 
     def _correct(self):
@@ -582,6 +626,53 @@ class RegionSuperResolver:
                                                                value_range, device=self.device)
                                        for name in ("model", "interpolated")}
         return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._distribution[key].items()}
+
+    def fit_quantile_map(self, hr_regions, bins: int = 256, on: str = "detail", value_range=None,
+                         tail_count: int = 16):
+        """Calibrate a srmi.quantile_map.QuantileMap on regions whose truth is known:
+        hr_regions, a sequence of [C, s h, s w] fp32 device tensors (NaN allowed: a pixel
+        counts where both binned values are finite).  Each is downsampled whole by
+        task.downsample_mode and super-resolved as ``score`` does, eagerly and with NO map
+        applied -- and, a deliberate step away from ``score``'s path on a resolver with
+        consistent=K, WITHOUT the consistency correction, because the map is applied to the
+        blended field before it and must be calibrated on what it will see -- then accumulated as (src 'model', truth hr_region, base
+        'interpolated'); the fitted map is returned, ready for RegionSuperResolver(...,
+        quantile_map=).  This object's own quantile_map, if any, is neither used nor changed.
+
+        value_range: one (lo, hi) pair or one per channel; None takes each channel's
+        NaN-aware min and max of the FIRST region's truth values (on="value") or truth detail,
+        hr_region - 'interpolated' (on="detail"), with torch -- a host read, at fit time
+        only.  Later regions that leave it land in the outer entries and map by the constant
+        shifts.  bins, on, tail_count: as QuantileMap takes them.
+
+        Out of scope: srmi.inference.TiledInference, training through the map, and a map
+        that varies in space or with the season."""
+        from .quantile_map import MODES, QuantileMap
+        if on not in MODES:
+            raise ValueError(f"on {on!r}: one of {MODES}")
+        regions = list(hr_regions)
+        if not regions:
+            raise ValueError("fit_quantile_map needs at least one region")
+        s, qm = self.s, None
+        for hr_region in regions:
+            if tuple(hr_region.shape) != (self.C, self.h * s, self.w * s):
+                raise ValueError(f"region shape {tuple(hr_region.shape)} != {(self.C, self.h * s, self.w * s)}")
+            hr = hr_region.contiguous()
+            self.region.copy_(downsample(hr[None], s, mode=self.dmode)[0])
+            self._run(use_map=False, correct=False)
+            model, interp = self.images["model"], self.images["interpolated"]
+            if qm is None:
+                if value_range is None:
+                    t = hr - interp if on == "detail" else hr
+                    t = t.reshape(self.C, -1)
+                    fin = torch.isfinite(t)
+                    lo = torch.where(fin, t, torch.full_like(t, float("inf"))).amin(1)
+                    hi = torch.where(fin, t, torch.full_like(t, float("-inf"))).amax(1)
+                    value_range = torch.stack([lo, hi], 1).cpu().numpy()
+                qm = QuantileMap(self.C, value_range, bins=bins, on=on, tail_count=tail_count, device=self.device)
+            qm.accumulate(model, hr, interp if on == "detail" else None)
+        qm.fit()
+        return qm
 
     def set_params(self, params: torch.Tensor) -> None:
         """Load new weights: copied into the parameter buffer the engines (and the

@@ -83,6 +83,20 @@ downsample, and ``score``'s RMSE against a synthetic truth for every arm; writes
 profiles/consistency_bench.json.  No pass / fail bar: none of it had been measured before,
 and the weights are default_init_'s, untrained -- the residuals and RMSEs describe the
 tool's network, not a trained one.
+
+--quantile-map: what does the quantile map cost, and what does it move?  A
+srmi.quantile_map.QuantileMap (256 bins, on="detail", tail_count 16) is fitted by
+``fit_quantile_map`` on one synthetic region and applied to another seed.  Reports the eager
+times of accumulate, fit and apply alone with the bytes each must move (accumulate: three
+reads of the field; apply: two reads and one write; value mode one read fewer) and the bytes/s
+they achieve beside the achievable bandwidth DESIGN.md section 3 uses, on the tool's images, a
+smooth field and white noise; srmi_distribution's range pass (two reads, nothing else),
+measured in the same run, as the pure-read yardstick; the region time with the map on and
+off, the arms alternating window by window on one device, beside the spread of the off
+windows; and 'q_bias', 'pss', 'w1' and the RMSE of 'model' against the held-out truth before
+and after, with consistent 0 and 3; writes profiles/quantile_map_bench.json.  No pass / fail
+bar.  The weights are default_init_'s, untrained: the numbers show the mechanism and make no
+claim of skill on real data.
 """
 import argparse
 import json
@@ -461,6 +475,145 @@ def distribution_main(a, spec, params, dev, kw):
     return res
 
 
+ACHIEVABLE_TB_PER_S = 6.3
+
+
+def quantile_map_main(a, spec, params, dev, kw):
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.distribution import DistributionScore
+    from srmi.quantile_map import QuantileMap
+    from srmi.superres import RegionSuperResolver
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    shape = (1, side, side)
+    hr_fit = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    hr_test = torch.tensor(synthetic_hr(1, 1, side, 97)[0]).to(dev)
+    BINS, TAIL, KC = 256, 16, 3
+
+    def make(**more):
+        return RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                                   graph=not a.no_graph, **more, **kw)
+
+    off = {0: make(), KC: make(consistent=KC)}
+    qm = off[0].fit_quantile_map([hr_fit], bins=BINS, on="detail", tail_count=TAIL)
+    on = {K: make(consistent=K, quantile_map=qm) for K in off}
+    arms = {"off": off[0], "on": on[0], f"off_consistent{KC}": off[KC], f"on_consistent{KC}": on[KC]}
+
+    # ---- what the map moves: the scores of 'model' against the held-out truth, every arm
+    def scores(rs):
+        images, losses, dist = rs.score_distribution(hr_test)
+        m = dist["model"]
+        return {"rmse_model": float(losses["model"]), "rmse_interpolated": float(losses["interpolated"]),
+                "pss": float(m["pss"]), "w1": float(m["w1"]), "under": float(m["under"]), "over": float(m["over"]),
+                "q_bias": [float(f"{v:.5g}") for v in m["q_bias"][0].tolist()]}
+
+    truth = {k: scores(rs) for k, rs in arms.items()}
+    probs = list(off[0]._distribution[next(iter(off[0]._distribution))]["model"].probs)
+    flat = int((qm.knots[0, 1:] == qm.knots[0, :-1]).sum())
+    lr_test = off[0].images["input"].clone()
+
+    # ---- the region with the map on and off, the arms alternating window by window
+    for rs in arms.values():
+        for _ in range(a.warmup):
+            out = rs.super_resolve(lr_test)
+        torch.cuda.synchronize()
+        if not bool(torch.isfinite(out["model"]).all()):
+            raise SystemExit("superres_bench: quantile map: non-finite output")
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in arms}
+    for _ in range(a.repeats):
+        for k, rs in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(a.regions):
+                rs.super_resolve(lr_test)
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.regions)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+
+    # ---- the launches alone, eager, on three kinds of field
+    lo, hi = float(hr_test.min()), float(hr_test.max())
+    g = torch.Generator(device=dev).manual_seed(7)
+    y = torch.arange(side, device=dev, dtype=torch.float64)[:, None] / side
+    x = torch.arange(side, device=dev, dtype=torch.float64)[None, :] / side
+    t = (torch.sin(2 * math.pi * (y / 1.7 + x / 3.1)) + 0.5 * torch.sin(2 * math.pi * (y / 0.9 - x / 1.3) + 1.0)
+         + 0.25 * torch.cos(2 * math.pi * (y / 0.6 + x / 0.45)))
+    t = (t - t.min()) / (t.max() - t.min())  # 0 .. 1
+    images = off[0].super_resolve(lr_test)
+    fields = {  # kind -> (src, truth, base); the detail is src - base
+        "synthetic": (images["model"].clone(), hr_test, images["interpolated"].clone()),
+        "smooth": ((lo + (hi - lo) * (0.1 + 0.8 * t)).float()[None].contiguous(),
+                   (lo + (hi - lo) * t).float()[None].contiguous(),
+                   torch.full(shape, lo + 0.5 * (hi - lo), device=dev)),
+        "white": (lo + (hi - lo) * torch.rand(shape, device=dev, generator=g),
+                  lo + (hi - lo) * torch.rand(shape, device=dev, generator=g),
+                  torch.full(shape, lo + 0.5 * (hi - lo), device=dev))}
+    HW4 = 4.0 * side * side
+    launches = {}
+    for kind, (src, tr, base) in fields.items():
+        d = src - base
+        rng_ = (float(d.min()), float(d.max()) + 1e-3)
+        q = {"detail": QuantileMap(1, rng_, bins=BINS, on="detail", tail_count=TAIL, device=dev),
+             "value": QuantileMap(1, (lo, hi), bins=BINS, on="value", tail_count=TAIL, device=dev)}
+        out = torch.empty_like(src)
+        for mode, m in q.items():
+            b = base if mode == "detail" else None
+            nread = 3 if mode == "detail" else 2
+
+            def acc(m=m, b=b):
+                m.reset()
+                m.accumulate(src, tr, b)
+            t_acc = timed(acc)
+            t_fit = timed(m.fit)
+            t_app = timed(lambda m=m, b=b: m.apply(src, b, out=out))
+            work = src.clone()
+            t_inp = timed(lambda m=m, b=b: m.apply(work, b, out=work))
+            moved = float((out - src).abs().mean())
+            launches[f"{kind}/{mode}"] = {
+                "accumulate_ms": round(t_acc, 4), "accumulate_bytes": int(nread * HW4),
+                "accumulate_gb_per_s": round(nread * HW4 / (t_acc * 1e-3) / 1e9, 1),
+                "fit_ms": round(t_fit, 4), "fit_bytes": int(2 * (BINS + 2) * 8 + (BINS + 3) * 12 + 16),
+                "apply_ms": round(t_app, 4), "apply_in_place_ms": round(t_inp, 4), "apply_bytes": int(nread * HW4),
+                "apply_gb_per_s": round(nread * HW4 / (t_app * 1e-3) / 1e9, 1),
+                "apply_share_of_achievable": round(nread * HW4 / (t_app * 1e-3) / 1e12 / ACHIEVABLE_TB_PER_S, 3),
+                "mean_abs_correction": float(f"{moved:.4g}")}
+        # the pure-read yardstick: srmi_distribution with and without its range pass, which reads two fields
+        free = DistributionScore(shape, bins=BINS, joint=0, device=dev)
+        given = DistributionScore(shape, bins=BINS, joint=0, value_range=(lo, hi), device=dev)
+        t_free, t_given = timed(lambda: free.measure(src, tr)), timed(lambda: given.measure(src, tr))
+        t_range = t_free - t_given  # a difference of two timings: it carries the noise of both
+        launches[f"{kind}/range_pass"] = {
+            "ms": round(t_range, 4), "score_ms": round(t_free, 4), "score_given_range_ms": round(t_given, 4),
+            "bytes": int(2 * HW4),
+            "gb_per_s": round(2 * HW4 / (t_range * 1e-3) / 1e9, 1) if t_range > 0 else None}
+
+    mpix = side * side / 1e6
+    ratios = {k: [p / q for p, q in zip(ms["on" + k], ms["off" + k])] for k in ("", f"_consistent{KC}")}
+    spread_off = {k: round((max(ms["off" + k]) - min(ms["off" + k])) / med["off" + k], 5) for k in ratios}
+    return {"tool": "superres_bench --quantile-map", "device": torch.cuda.get_device_name(0),
+            "config": {"workload": f"rcan-10-20-64 super_resolve, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR tile "
+                                   f"{a.tile}, overlap {r}; QuantileMap bins {BINS}, on=detail, tail_count {TAIL}, "
+                                   f"fitted on one synthetic region (seed 98), applied to another (seed 97)",
+                       "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                       "regions_per_window": a.regions, "achievable_tb_per_s": ACHIEVABLE_TB_PER_S,
+                       "fields": {"synthetic": "'model', the synthetic truth and 'interpolated' of the held-out region",
+                                  "smooth": "sinusoids as long as the region, the source pulled to the mean, a "
+                                            "constant base", "white": "uniform noise, a constant base"},
+                       "weights": "default_init_ (untrained): the numbers show the mechanism and make no claim of "
+                                  "skill on real data; no pass / fail bar"},
+            "hr_mpix_per_region": round(mpix, 3),
+            "region_ms": {k: {"median": round(med[k], 3), "min_max": [round(min(v), 3), round(max(v), 3)]}
+                          for k, v in ms.items()},
+            "on_over_off": {("consistent0" if k == "" else k[1:]): {
+                "median": round(statistics.median(v), 5), "min_max": [round(min(v), 5), round(max(v), 5)],
+                "spread_of_off_windows": spread_off[k]} for k, v in ratios.items()},
+            "map": {"range": [float(v) for v in qm.range[0]], "count": int(qm.count[0]),
+                    "shift_below": float(qm.meta[0, 2]), "shift_above": float(qm.meta[0, 3]),
+                    "flat_knot_intervals": flat}, "probs": probs,
+            "scores_of_model_against_held_out_truth": truth, "launches": launches}
+
+
 def ensemble_main(a, spec, params, lr, dev, kw):
     from oracle.rcan_oracle import synthetic_hr
     from srmi.superres import RegionSuperResolver
@@ -616,13 +769,17 @@ def main():
                     help="time RegionSuperResolver(ensemble=K) for each K (1 is always among them)")
     ap.add_argument("--consistent", type=int, nargs="+", default=None, metavar="K", choices=range(17),
                     help="time RegionSuperResolver(consistent=K) for each K (0 is always among them)")
+    ap.add_argument("--quantile-map", action="store_true",
+                    help="time the quantile map's launches and the region with the map on and off, and score both")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
                                                 "spectra_bench.json, ssim_bench.json, distribution_bench.json, "
-                                                "ensemble_bench.json, consistency_bench.json)")
+                                                "ensemble_bench.json, consistency_bench.json, "
+                                                "quantile_map_bench.json)")
     a = ap.parse_args()
-    if sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution > 1:
-        raise SystemExit("superres_bench: --land, --spectra, --ssim, --distribution, --ensemble and --consistent are "
-                         "separate runs")
+    if (sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution
+            + a.quantile_map > 1):
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --distribution, --ensemble, --consistent and "
+                         "--quantile-map are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
@@ -631,7 +788,8 @@ def main():
                              "ssim_bench.json" if a.ssim else
                              "distribution_bench.json" if a.distribution else
                              "ensemble_bench.json" if a.ensemble is not None else
-                             "consistency_bench.json" if a.consistent is not None else "superres_bench.json")
+                             "consistency_bench.json" if a.consistent is not None else
+                             "quantile_map_bench.json" if a.quantile_map else "superres_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("superres_bench: no GPU (there is no CPU path to time)")
     from oracle.rcan_oracle import synthetic_hr
@@ -648,12 +806,13 @@ def main():
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
     if (a.land is not None or a.spectra is not None or a.ssim or a.distribution or a.ensemble is not None
-            or a.consistent is not None):
+            or a.consistent is not None or a.quantile_map):
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
                           ssim_main(a, spec, params, dev, kw) if a.ssim else
                           distribution_main(a, spec, params, dev, kw) if a.distribution else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
+                          quantile_map_main(a, spec, params, dev, kw) if a.quantile_map else
                           consistency_main(a, spec, params, lr, dev, kw))
         print(line)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
