@@ -29,8 +29,7 @@
 
 namespace srmi {
 
-static unsigned long long* g_debug_stamps = nullptr;
-void conv3x3_set_debug_stamps(unsigned long long* buf) { g_debug_stamps = buf; }
+static unsigned long long* g_debug_stamps = nullptr;  // (srmi_debug_conv_stamps, below, sets it)
 unsigned long long* conv3x3_debug_stamps() { return g_debug_stamps; }
 // diagnostic build: SRMI_STAMP_EPI=<epilogue> stamps only that epilogue's launches
 unsigned long long* conv3x3_stamps_for(int epi) {
@@ -488,3 +487,15 @@ int conv3x3_nstrips(int H, int W) {
 }
 
 }  // namespace srmi
+
+using namespace srmi;
+
+extern "C" {
+
+// diagnostic only: s_memtime stamps of the conv kernel (64 per workgroup), NULL = off
+int srmi_debug_conv_stamps(void* buf) {
+  g_debug_stamps = (unsigned long long*)buf;
+  return 0;
+}
+
+}  // extern "C"

@@ -418,8 +418,13 @@ int dist_plan(int C, int H, int W, int B, int J, DistPlan* p) {
 }
 
 }  // namespace
+}  // namespace srmi
 
-int distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes) {
   DistPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = dist_plan(C, H, W, nbins, njoint, &p);
@@ -428,9 +433,9 @@ int distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* b
   return 0;
 }
 
-int distribution_launch(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
-                        const double* probs, int nprobs, void* ws, size_t ws_bytes, long long* hist, long long* joint,
-                        float* range, long long* count, double* derived, int flags, hipStream_t st) {
+int srmi_distribution(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
+                      const double* probs, int nprobs, void* ws, size_t ws_bytes, long long* hist, long long* joint,
+                      float* range, long long* count, double* derived, int flags, void* stream) {
   DistPlan p;
   if (!a || !b || !ws || !hist || !range || !count || !derived || ((uintptr_t)ws & 15) != 0) return SRMI_ERR_ARG;
   if (flags & ~(SRMI_DISTRIBUTION_MERGE_RUNS | SRMI_DISTRIBUTION_ONE_COPY | SRMI_DISTRIBUTION_COPY_BY_WAVE))
@@ -456,6 +461,7 @@ int distribution_launch(const float* a, const float* b, int C, int H, int W, int
   char* base = static_cast<char*>(ws);
   int* part = reinterpret_cast<int*>(base);
   float* mm = reinterpret_cast<float*>(base + p.off_mm);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (!lo_hi) {
     hipLaunchKernelGGL(dist_range_kernel, dim3((unsigned)(C * p.nblk_r)), dim3(kRangeThreads), 0, st, a, b, p.HW,
                        p.nblk_r, mm);
@@ -479,4 +485,4 @@ int distribution_launch(const float* a, const float* b, int C, int H, int W, int
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -1355,99 +1355,11 @@ int srmi_rmse_partial_masked(srmi_engine* e, const float* pred, const float* tar
   return sqerr_masked_launch(pred, target, n, reinterpret_cast<double*>(e->lpart), e->lpart_n / 4, loss4, S_(stream));
 }
 
-int srmi_rmse_finalize(float* loss4, void* stream) {
-  if (!loss4) return SRMI_ERR_ARG;
-  return loss_finalize_launch(loss4, LOSS_RMSE, S_(stream));
-}
-
 int srmi_charbonnier_partial(srmi_engine* e, const float* pred, const float* target, size_t n, double count_global,
                              float eps, float* loss4, float* dy, void* stream) {
   if (!e || !pred || !target || (!loss4 && !dy) || count_global <= 0) return SRMI_ERR_ARG;
   RC(charb_partial_launch(pred, target, n, eps, count_global, dy, loss4 ? e->lpart : nullptr, e->lpart_n, S_(stream)));
   return loss4 ? sqerr_finish_launch(e->lpart, e->lpart_n, count_global, loss4, S_(stream)) : 0;
-}
-
-int srmi_loss_finalize(float* loss4, int kind, void* stream) {
-  if (!loss4 || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
-  return loss_finalize_launch(loss4, kind, S_(stream));
-}
-
-int srmi_batch_losses(const float* pred, const float* target, int ntiles, long long tile_elems, int batch_size,
-                      int kind, float eps, float* work, float* out, void* stream) {
-  if (!pred || !target || !work || !out || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
-  return batch_losses_launch(pred, target, ntiles, tile_elems, batch_size, kind, eps, work, out, S_(stream));
-}
-
-int srmi_tile_loss_parts(const float* pred, const float* target, int ntiles, long long tile_elems, int kind,
-                         float eps, float* parts, void* stream) {
-  if (!pred || !target || !parts || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
-  return tile_loss_parts_launch(pred, target, ntiles, tile_elems, kind, eps, parts, S_(stream));
-}
-
-int srmi_loss_from_parts(const float* parts, int ntiles, double count_global, int kind, float* loss4, void* stream) {
-  if (!parts || !loss4 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
-  return loss_from_parts_launch(parts, ntiles * kTileSub, count_global, kind, loss4, S_(stream));
-}
-
-int srmi_batch_loss_means(const float* sums, int ntiles, long long tile_elems, int batch_size, int kind, float* out,
-                          void* stream) {
-  if (!sums || !out || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
-  return batch_loss_means_launch(sums, ntiles, tile_elems, batch_size, kind, out, S_(stream));
-}
-
-int srmi_loss_combine(float* loss4, const float* parts4, int nparts, int kind, void* stream) {
-  if (!loss4 || !parts4 || nparts < 1 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
-  return loss_combine_launch(loss4, parts4, nparts, kind, S_(stream));
-}
-
-int srmi_downsample(const float* hr, int N, int C, int H, int W, int scale, float* lr, void* stream) {
-  return downsample_launch(hr, N, C, H, W, scale, lr, S_(stream));
-}
-
-int srmi_upsample(const float* lr, int N, int C, int h, int w, int scale, float* hr, void* stream) {
-  return upsample_launch(lr, N, C, h, w, scale, hr, S_(stream));
-}
-
-int srmi_interpolate(const float* x, int N, int C, int H, int W, int Ho, int Wo, float rh, float rw, int mode, float* y,
-                     void* stream) {
-  return interp_launch(x, N, C, H, W, Ho, Wo, rh, rw, mode, y, S_(stream));
-}
-
-int srmi_adam_step(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, void* stream) {
-  if (step < 1) return SRMI_ERR_ARG;
-  const double bc1 = 1.0 - std::pow((double)beta1, step);
-  const double bc2 = 1.0 - std::pow((double)beta2, step);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)std::sqrt(bc2);
-  return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, S_(stream));
-}
-
-int srmi_grad_norm_workspace(size_t n, size_t* bytes) {
-  if (!bytes || n < 1) return SRMI_ERR_ARG;
-  *bytes = grad_norm_blocks(n) * sizeof(double);
-  return 0;
-}
-
-int srmi_grad_norm(const float* g, size_t n, float max_norm, void* workspace, size_t ws_bytes, float* ctl,
-                   void* stream) {
-  if (!g || !workspace || !ctl || n < 1 || !(max_norm > 0.f)) return SRMI_ERR_ARG;  // (a NaN max_norm too)
-  if (ws_bytes < grad_norm_blocks(n) * sizeof(double) || ((size_t)workspace & 7) || ((size_t)g & 3))
-    return SRMI_ERR_ARG;
-  return grad_norm_launch(g, n, max_norm, (double*)workspace, ctl, S_(stream));
-}
-
-int srmi_adam_step_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, int step, float lr,
-                           float beta1, float beta2, float eps, float weight_decay, float ema_decay, const float* ctl,
-                           void* stream) {
-  if (step < 1 || !ctl) return SRMI_ERR_ARG;
-  if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return SRMI_ERR_ARG;
-  const double bc1 = 1.0 - std::pow((double)beta1, step);
-  const double bc2 = 1.0 - std::pow((double)beta2, step);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)std::sqrt(bc2);
-  return adam_guarded_launch(p, g, m, v, ema, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, ema_decay, ctl,
-                             S_(stream));
 }
 
 // ---------------------------------------------------------------- op level
@@ -1479,23 +1391,6 @@ int srmi_conv3x3(const void* x, const void* wpack, const float* bias, int N, int
 }
 
 int srmi_conv3x3_nstrips(int H, int W) { return conv3x3_nstrips(H, W); }
-
-// diagnostic only: s_memtime stamps of the conv kernel (64 per workgroup), NULL = off
-int srmi_debug_conv_stamps(void* buf) {
-  conv3x3_set_debug_stamps((unsigned long long*)buf);
-  return 0;
-}
-
-int srmi_debug_wgrad_stamps(void* buf) {
-  wgrad3x3_set_debug_stamps((unsigned long long*)buf);
-  return 0;
-}
-
-int srmi_pack_conv(const float* w, const float* b, int Cout, int Cin, int ps, void* fpack, void* dpack, float* pbias,
-                   int dtype, void* stream) {
-  if (dtype != SRMI_DTYPE_BF16 && dtype != SRMI_DTYPE_F32) return SRMI_ERR_ARG;
-  return pack_one_launch(w, b, Cout, Cin, ps, fpack, dpack, pbias, dtype == SRMI_DTYPE_F32, S_(stream));
-}
 
 int srmi_wgrad3x3(const void* x, const void* dy, int N, int H, int W, int Cout, int dy_unshuffle, int row_splits,
                   float* slab, size_t slab_bytes, int ps, float alpha, float* gw, float* gb, int dtype, void* stream) {
@@ -1554,256 +1449,6 @@ int srmi_tail_forward(const void* x, const float* w, const float* b, int N, int 
                       void* stream) {
   if (dtype != SRMI_DTYPE_BF16 && dtype != SRMI_DTYPE_F32) return SRMI_ERR_ARG;
   return tail_fwd_launch(x, w, b, N, C, H, W, y, dtype == SRMI_DTYPE_F32, S_(stream));
-}
-
-int srmi_llc_index_map_workspace(long long n_template, size_t* bytes) {
-  if (!bytes) return SRMI_ERR_ARG;
-  return llc_index_map_workspace(n_template, bytes);
-}
-
-int srmi_llc_index_map(const void* template_be, long long n_template, int nx, int y0, int ys, int x0, int xs,
-                       int* idx_map, long long* n_wet, void* workspace, size_t workspace_bytes, void* stream) {
-  return llc_index_map_launch(static_cast<const uint32_t*>(template_be), n_template, nx, y0, ys, x0, xs, idx_map,
-                              n_wet, workspace, workspace_bytes, S_(stream));
-}
-
-int srmi_llc_gather(const void* data_be, long long n_values, const int* idx_map, long long npix, float* out,
-                    void* stream) {
-  return llc_gather_launch(static_cast<const uint32_t*>(data_be), n_values, idx_map, npix, out, S_(stream));
-}
-
-int srmi_tiles_nonfinite(const float* region, int C, int H, int W, int ty, int tx, int* bad, void* stream) {
-  return tiles_nonfinite_launch(region, C, H, W, ty, tx, bad, S_(stream));
-}
-
-int srmi_tiles_gather(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
-                      float* out, void* stream) {
-  return tiles_gather_launch(region, C, H, W, ty, tx, src, nslots, out, S_(stream));
-}
-
-int srmi_llc_block_mask(const int* idx_map, long long npix, int block_shift, int* mask, int n_blocks, void* stream) {
-  return llc_block_mask_launch(idx_map, npix, block_shift, mask, n_blocks, S_(stream));
-}
-
-int srmi_llc_compact_map(const int* idx_map, long long npix, int block_shift, const int* block_base, int n_blocks,
-                         int* idx_out, void* stream) {
-  return llc_compact_map_launch(idx_map, npix, block_shift, block_base, n_blocks, idx_out, S_(stream));
-}
-
-int srmi_tiles_keep(const int* bad, int C, int ncells, int* src, int* count, void* stream) {
-  return tiles_keep_launch(bad, C, ncells, src, count, S_(stream));
-}
-
-int srmi_tiles_gather_dev(const float* region, int C, int H, int W, int ty, int tx, const int* src, const int* count,
-                          int max_slots, float* out, void* stream) {
-  return tiles_gather_dev_launch(region, C, H, W, ty, tx, src, count, max_slots, out, S_(stream));
-}
-
-int srmi_batch_prep(const float* raw, int B, int C, int T, int flip_index, int scale, float* hr, float* lr,
-                    float* mean, float* std, void* stream) {
-  return batch_prep_launch(raw, B, C, T, flip_index, scale, hr, lr, mean, std, S_(stream));
-}
-
-int srmi_batch_prep_norm(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
-                         const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
-                         void* stream) {
-  return batch_prep_norm_launch(raw, B, C, T, flip_index, scale, mode, off, div, hr, lr, off_out, div_out,
-                                S_(stream));
-}
-
-int srmi_region_to_tiles_norm(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
-                              const float* div, float* tiles, float* off_out, float* div_out, int* bad,
-                              void* stream) {
-  return region_to_tiles_norm_launch(region, C, H, W, ty, tx, mode, off, div, tiles, off_out, div_out, bad,
-                                     S_(stream));
-}
-
-int srmi_overlap_count(int L, int t, int S) { return overlap_count(L, t, S); }
-
-int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
-                                 const float* off, const float* div, float* tiles, float* off_out, float* div_out,
-                                 int* bad, void* stream) {
-  return region_to_tiles_overlap_launch(region, C, H, W, ty, tx, sy, sx, mode, off, div, tiles, off_out, div_out, bad,
-                                        S_(stream));
-}
-
-int srmi_tiles_blend(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty, int Tx,
-                     int Sy, int Sx, int Ho, int Wo, float* out, void* stream) {
-  return tiles_blend_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, out, S_(stream));
-}
-
-int srmi_region_to_tiles_overlap_masked(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
-                                        int mode, const float* off, const float* div, float* tiles, float* off_out,
-                                        float* div_out, int* bad, int min_wet, int* nwet, void* stream) {
-  return region_to_tiles_overlap_masked_launch(region, C, H, W, ty, tx, sy, sx, mode, off, div, tiles, off_out,
-                                               div_out, bad, min_wet, nwet, S_(stream));
-}
-
-int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* div, const int* bad, int C, int Ty,
-                            int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
-                            void* stream) {
-  return tiles_blend_masked_launch(tiles, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, S_(stream));
-}
-
-int srmi_tiles_dihedral(const float* in, long long nplanes, int h, int w, int variants, float* out, void* stream) {
-  return tiles_dihedral_launch(in, nplanes, h, w, variants, out, S_(stream));
-}
-
-int srmi_tiles_blend_ensemble(const float* tiles, int variants, const float* off, const float* div, const int* bad,
-                              int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale,
-                              float* mean, float* spread, void* stream) {
-  return tiles_blend_ensemble_launch(tiles, variants, off, div, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, mean,
-                                     spread, S_(stream));
-}
-
-int srmi_tiles_dry(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
-                   void* stream) {
-  return tiles_dry_launch(region, C, H, W, ty, tx, min_wet, bad, nwet, S_(stream));
-}
-
-int srmi_tiles_fill(float* tiles, long long nplanes, int h, int w, int* passes, void* stream) {
-  return tiles_fill_launch(tiles, nplanes, h, w, passes, S_(stream));
-}
-
-int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes) {
-  return spectra_workspace(C, H, W, P, Q, bytes);
-}
-
-int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* workspace,
-                 size_t workspace_bytes, float* out, int* nused, void* stream) {
-  return spectra_launch(a, b, C, H, W, P, Q, workspace, workspace_bytes, out, nused, S_(stream));
-}
-
-int srmi_ssim_workspace(int C, int H, int W, size_t* bytes) { return ssim_workspace(C, H, W, bytes); }
-
-int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_range, void* workspace,
-              size_t workspace_bytes, float* out, long long* count, float* map, void* stream) {
-  return ssim_launch(a, b, C, H, W, data_range, workspace, workspace_bytes, out, count, map, S_(stream));
-}
-
-int srmi_distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes) {
-  return distribution_workspace(C, H, W, nbins, njoint, bytes);
-}
-
-int srmi_distribution(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
-                      const double* probs, int nprobs, void* workspace, size_t workspace_bytes, long long* hist,
-                      long long* joint, float* range, long long* count, double* derived, int flags, void* stream) {
-  return distribution_launch(a, b, C, H, W, nbins, njoint, lo_hi, probs, nprobs, workspace, workspace_bytes, hist,
-                             joint, range, count, derived, flags, S_(stream));
-}
-
-int srmi_quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes) {
-  return quantile_map_accumulate_workspace(C, H, W, nbins, bytes);
-}
-
-int srmi_quantile_map_accumulate(const float* src, const float* truth, const float* base, int C, int H, int W,
-                                 int nbins, const float* range, int first, void* workspace, size_t workspace_bytes,
-                                 long long* hist, long long* count, void* stream) {
-  return quantile_map_accumulate_launch(src, truth, base, C, H, W, nbins, range, first, workspace, workspace_bytes,
-                                        hist, count, S_(stream));
-}
-
-int srmi_quantile_map_fit(const long long* hist, const long long* count, int C, int nbins, const float* range,
-                          long long tail_count, double* knots, float* table, float* meta, void* stream) {
-  return quantile_map_fit_launch(hist, count, C, nbins, range, tail_count, knots, table, meta, S_(stream));
-}
-
-int srmi_quantile_map_apply(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
-                            const float* meta, float strength, float* out, void* stream) {
-  return quantile_map_apply_launch(x, base, C, H, W, nbins, table, meta, strength, out, S_(stream));
-}
-
-int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
-  return spectral_loss_workspace(nplanes, H, W, P, Q, bytes);
-}
-
-int srmi_spectral_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
-                             float eps, float* parts, float* cparts, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-  return spectral_loss_parts_launch(pred, target, nplanes, H, W, P, Q, eps, parts, cparts, workspace, workspace_bytes,
-                                    S_(stream));
-}
-
-int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
-                                  const float* loss4, float* spec4, float* total, void* stream) {
-  return spectral_loss_from_parts_launch(parts, cparts, nplanes, P, weight, loss4, spec4, total, S_(stream));
-}
-
-int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long long nplanes, int H, int W, int P, int Q,
-                          float weight, const float* spec4, float* dy, void* stream) {
-  return spectral_loss_dy_launch(workspace, workspace_bytes, nplanes, H, W, P, Q, weight, spec4, dy, S_(stream));
-}
-
-int srmi_ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes) {
-  return ssim_loss_workspace(nplanes, H, W, bytes);
-}
-
-int srmi_ssim_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
-                         float* parts, float* cparts, void* workspace, size_t workspace_bytes, void* stream) {
-  return ssim_loss_parts_launch(pred, target, nplanes, H, W, data_range, parts, cparts, workspace, workspace_bytes,
-                                S_(stream));
-}
-
-int srmi_ssim_loss_from_parts(const float* parts, const float* cparts, long long nplanes, float weight,
-                              const float* base, float* ssim4, float* total, void* stream) {
-  return ssim_loss_from_parts_launch(parts, cparts, nplanes, weight, base, ssim4, total, S_(stream));
-}
-
-int srmi_ssim_loss_dy(const void* workspace, size_t workspace_bytes, const float* pred, const float* target,
-                      long long nplanes, int H, int W, float weight, const float* ssim4, float* dy, void* stream) {
-  return ssim_loss_dy_launch(workspace, workspace_bytes, pred, target, nplanes, H, W, weight, ssim4, dy, S_(stream));
-}
-
-int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip_index, int scale, int mode,
-                           const float* off, const float* div, float* hr, float* lr, float* off_out, float* div_out,
-                           int* nwet, void* stream) {
-  return batch_prep_masked_launch(raw, B, C, T, flip_index, scale, mode, off, div, hr, lr, off_out, div_out, nwet,
-                                  S_(stream));
-}
-
-int srmi_tile_loss_parts_masked(const float* pred, const float* target, int ntiles, long long tile_elems, int kind,
-                                float eps, float* parts, float* cparts, void* stream) {
-  if (!pred || !target || !parts || !cparts || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN))
-    return SRMI_ERR_ARG;
-  return tile_loss_parts_masked_launch(pred, target, ntiles, tile_elems, kind, eps, parts, cparts, S_(stream));
-}
-
-int srmi_loss_from_parts_masked(const float* parts, const float* cparts, int ntiles, int kind, float* loss4,
-                                void* stream) {
-  if (!parts || !cparts || !loss4 || ntiles < 1 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
-  return loss_from_parts_masked_launch(parts, cparts, ntiles * kTileSub, kind, loss4, S_(stream));
-}
-
-int srmi_loss_dy_masked(const float* pred, const float* target, size_t n, int kind, float eps, const float* loss4,
-                        float* dy, void* stream) {
-  if (!pred || !target || !loss4 || !dy || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
-  return loss_dy_masked_launch(pred, target, n, kind, eps, loss4, dy, S_(stream));
-}
-
-int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {
-  return tile_stats_launch(tiles, n, C, ty, tx, acc, first, S_(stream));
-}
-
-int srmi_tile_stats_finalize(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
-                             void* stream) {
-  return tile_stats_finalize_launch(acc, n, C, ntimes, tstats, gstats, S_(stream));
-}
-
-int srmi_region_to_tiles(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
-                         float* std, int* bad, void* stream) {
-  if (!region || !tiles || !mean || !std) return SRMI_ERR_ARG;
-  return region_to_tiles_launch(region, C, H, W, ty, tx, tiles, mean, std, bad, S_(stream));
-}
-
-int srmi_tiles_to_region(const float* tiles, const float* mean, const float* std, const int* inv, int C, int ty,
-                         int tx, int gy, int gx, float* out, void* stream) {
-  if (!tiles || !out || (mean && !std)) return SRMI_ERR_ARG;
-  return tiles_to_region_launch(tiles, mean, std, inv, C, ty, tx, gy, gx, out, S_(stream));
-}
-
-int srmi_axpy(float* y, const float* x, float a, size_t n, void* stream) {
-  if (!y || !x) return SRMI_ERR_ARG;
-  return scale_add_launch(y, x, a, n, S_(stream));
 }
 
 }  // extern "C"

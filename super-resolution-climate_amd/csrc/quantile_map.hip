@@ -415,8 +415,13 @@ int qm_ranges(const float* range, int C, QmRanges* rg) {
 bool qm_overlap(const float* p, const float* q, size_t n) { return p < q + n && q < p + n; }
 
 }  // namespace
+}  // namespace srmi
 
-int quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes) {
   QmPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = qm_plan(C, H, W, nbins, &p);
@@ -425,9 +430,9 @@ int quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* by
   return 0;
 }
 
-int quantile_map_accumulate_launch(const float* src, const float* truth, const float* base, int C, int H, int W,
-                                   int nbins, const float* range, int first, void* ws, size_t ws_bytes,
-                                   long long* hist, long long* count, hipStream_t st) {
+int srmi_quantile_map_accumulate(const float* src, const float* truth, const float* base, int C, int H, int W,
+                                 int nbins, const float* range, int first, void* ws, size_t ws_bytes,
+                                 long long* hist, long long* count, void* stream) {
   QmPlan p;
   QmRanges rg;
   if (!src || !truth || !ws || !hist || !count || ((uintptr_t)ws & 15) != 0) return SRMI_ERR_ARG;
@@ -438,6 +443,7 @@ int quantile_map_accumulate_launch(const float* src, const float* truth, const f
   if (ws_bytes < p.bytes) return SRMI_ERR_ARG;
   int* part = static_cast<int*>(ws);
   const size_t lds = (size_t)p.R * p.stride * sizeof(unsigned int);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (base)
     hipLaunchKernelGGL(qm_hist_kernel<true>, dim3((unsigned)(C * p.nblk)), dim3(kQmThreads), lds, st, src, truth, base,
                        p.HW, p.nblk, nbins, rg, p.R, p.stride, p.Wp, part);
@@ -451,21 +457,22 @@ int quantile_map_accumulate_launch(const float* src, const float* truth, const f
   return 0;
 }
 
-int quantile_map_fit_launch(const long long* hist, const long long* count, int C, int nbins, const float* range,
-                            long long tail_count, double* knots, float* table, float* meta, hipStream_t st) {
+int srmi_quantile_map_fit(const long long* hist, const long long* count, int C, int nbins, const float* range,
+                          long long tail_count, double* knots, float* table, float* meta, void* stream) {
   QmRanges rg;
   if (!hist || !count || !knots || !table || !meta) return SRMI_ERR_ARG;
   if (C < 1 || C > kQmMaxC || nbins < 2 || nbins > kQmMaxBins || tail_count < 0) return SRMI_ERR_ARG;
   const int rc = qm_ranges(range, C, &rg);
   if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(qm_fit_kernel, dim3((unsigned)C), dim3(kQmThreads), 0, st, hist, nbins, rg, tail_count, knots,
                      table, meta);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-int quantile_map_apply_launch(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
-                              const float* meta, float strength, float* out, hipStream_t st) {
+int srmi_quantile_map_apply(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
+                            const float* meta, float strength, float* out, void* stream) {
   if (!x || !table || !meta || !out) return SRMI_ERR_ARG;
   if (C < 1 || C > kQmMaxC || H < 1 || W < 1 || nbins < 2 || nbins > kQmMaxBins) return SRMI_ERR_ARG;
   const long long HW = (long long)H * W;
@@ -477,6 +484,7 @@ int quantile_map_apply_launch(const float* x, const float* base, int C, int H, i
   const long long nb = (HW + kQmApplySpan - 1) / kQmApplySpan;
   const int nblk = (int)(nb < kQmApplyBlocks ? nb : kQmApplyBlocks);
   const size_t lds = (size_t)(nbins + 2) * sizeof(float2);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (base)
     hipLaunchKernelGGL(qm_apply_kernel<true>, dim3((unsigned)(C * nblk)), dim3(kQmApplyThreads), lds, st, x, base, HW,
                        nblk, nbins, table, meta, strength, out);
@@ -487,4 +495,4 @@ int quantile_map_apply_launch(const float* x, const float* base, int C, int H, i
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -722,15 +722,6 @@ __global__ void downsample_kernel(const float* __restrict__ hr, int NC, int H, i
   }
 }
 
-int downsample_launch(const float* hr, int N, int C, int H, int W, int scale, float* lr, hipStream_t st) {
-  if (scale < 2 || H % scale || W % scale || N < 1 || C < 1) return SRMI_ERR_SHAPE;
-  const int plane = (H / scale) * (W / scale);
-  const int gy = N * C < kMaxGridY ? N * C : kMaxGridY;
-  hipLaunchKernelGGL(downsample_kernel, dim3((plane + 255) / 256, gy), dim3(256), 0, st, hr, N * C, H, W, scale, lr);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 __device__ __forceinline__ void cubic_w(float t, float* c) {
   const float A = -0.75f;
   float x1 = t + 1.f;
@@ -771,15 +762,6 @@ __global__ void upsample_kernel(const float* __restrict__ lr, int NC, int h, int
     }
     hr[nc * H * W + i] = acc;
   }
-}
-
-int upsample_launch(const float* lr, int N, int C, int h, int w, int scale, float* hr, hipStream_t st) {
-  if (scale < 1 || N < 1 || C < 1) return SRMI_ERR_SHAPE;
-  const int plane = h * scale * w * scale;
-  const int gy = N * C < kMaxGridY ? N * C : kMaxGridY;
-  hipLaunchKernelGGL(upsample_kernel, dim3((plane + 255) / 256, gy), dim3(256), 0, st, lr, N * C, h, w, scale, hr);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // F.interpolate(x, scale_factor, mode, align_corners=False) at any factor, the form
@@ -826,17 +808,6 @@ __global__ void interp_kernel(const float* __restrict__ x, int NC, int H, int W,
     acc += wy[i] * rsum;
   }
   y[idx] = acc;
-}
-
-int interp_launch(const float* x, int N, int C, int H, int W, int Ho, int Wo, float rh, float rw, int mode, float* y,
-                  hipStream_t st) {
-  if (!x || !y || (mode != 1 && mode != 2)) return SRMI_ERR_ARG;
-  if (N < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || !(rh > 0.f) || !(rw > 0.f)) return SRMI_ERR_SHAPE;
-  const size_t tot = (size_t)N * C * Ho * Wo;
-  hipLaunchKernelGGL(interp_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, x, N * C, H, W, Ho, Wo, rh, rw, mode,
-                     y);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // ============================================================================ loss
@@ -1014,7 +985,7 @@ __device__ __forceinline__ void loss_finalize_one(float* loss, int kind) {
 
 __global__ void loss_finalize_kernel(float* loss, int kind) { loss_finalize_one(loss, kind); }
 
-int loss_finalize_launch(float* loss, int kind, hipStream_t st) {
+static int loss_finalize_launch(float* loss, int kind, hipStream_t st) {
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, st, loss, kind);
   SRMI_CHECK_LAUNCH();
   return 0;
@@ -1028,12 +999,6 @@ __global__ void loss_combine_kernel(float* loss, const float* __restrict__ parts
   loss[0] = s;
   loss[1] = parts[1];
   if (kind >= 0) loss_finalize_one(loss, kind);
-}
-
-int loss_combine_launch(float* loss, const float* parts, int nparts, int kind, hipStream_t st) {
-  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(1), 0, st, loss, parts, nparts, kind);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // Per-batch losses of ModelTrainer.process_image / evaluate (sres/controller/
@@ -1118,26 +1083,13 @@ __global__ void __launch_bounds__(256) batch_loss_mean_kernel(const float* __res
   }
 }
 
-int batch_losses_launch(const float* y, const float* t, int ntiles, long long tile_elems, int bs, int kind, float eps,
-                        float* work, float* out, hipStream_t st) {
-  if (ntiles < 1 || tile_elems < 1 || bs < 1 || (ntiles + bs - 1) / bs > 1024) return SRMI_ERR_SHAPE;
-  if (tile_elems % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)t & 15) == 0)
-    hipLaunchKernelGGL(tile_loss_sums_v4_kernel, dim3(ntiles), dim3(1024), 0, st, reinterpret_cast<const float4*>(y),
-                       reinterpret_cast<const float4*>(t), tile_elems / 4, kind, eps, work);
-  else
-    hipLaunchKernelGGL(tile_loss_sums_kernel, dim3(ntiles), dim3(256), 0, st, y, t, tile_elems, kind, eps, work);
-  SRMI_CHECK_LAUNCH();
-  hipLaunchKernelGGL(batch_loss_mean_kernel, dim3(1), dim3(256), 0, st, work, ntiles, tile_elems, bs, kind, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // Loss sums invariant to how the batch is split over micro-batch engines (and over
 // calls): every tile's elements are summed by kTileSub blocks over fixed slices with a
 // fixed reduction tree, into parts[tile][kTileSub]; the whole batch's S is then the sum
 // of all parts in tile order, in fp64 (loss_from_parts).  So one engine of B tiles and
 // two of B/2 give a bit-identical loss -- and loss scale 1/(count L), which the bf16
 // gradient maps would otherwise turn from a 1-ulp difference into 1e-5-level noise.
+constexpr int kTileSub = 16;
 __global__ void __launch_bounds__(256) tile_loss_parts_kernel(const float* __restrict__ y, const float* __restrict__ t,
                                                               long long tile_elems, int kind, float eps,
                                                               float* __restrict__ parts) {
@@ -1155,15 +1107,6 @@ __global__ void __launch_bounds__(256) tile_loss_parts_kernel(const float* __res
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) parts[(size_t)tile * kTileSub + sub] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-int tile_loss_parts_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind, float eps,
-                           float* parts, hipStream_t st) {
-  if (ntiles < 1 || tile_elems < 1) return SRMI_ERR_SHAPE;
-  hipLaunchKernelGGL(tile_loss_parts_kernel, dim3(kTileSub, ntiles), dim3(256), 0, st, y, t, tile_elems, kind, eps,
-                     parts);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // loss4 from the parts of loss_from_parts' tiles: [0] = S (fp64 sum in part order),
@@ -1187,13 +1130,6 @@ __global__ void __launch_bounds__(256) loss_from_parts_kernel(const float* __res
     loss[1] = (float)count;
     if (kind >= 0) loss_finalize_one(loss, kind);
   }
-}
-
-int loss_from_parts_launch(const float* parts, int nparts, double count, int kind, float* loss, hipStream_t st) {
-  if (nparts < 1 || count <= 0) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(loss_from_parts_kernel, dim3(1), dim3(256), 0, st, parts, nparts, count, kind, loss);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // The three above for training on tiles with land (no reference counterpart: the
@@ -1237,15 +1173,6 @@ __global__ void __launch_bounds__(256) tile_loss_parts_masked_kernel(const float
   }
 }
 
-int tile_loss_parts_masked_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind,
-                                  float eps, float* parts, float* cparts, hipStream_t st) {
-  if (ntiles < 1 || tile_elems < 1) return SRMI_ERR_SHAPE;
-  hipLaunchKernelGGL(tile_loss_parts_masked_kernel, dim3(kTileSub, ntiles), dim3(256), 0, st, y, t, tile_elems, kind,
-                     eps, parts, cparts);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // loss_from_parts_kernel with the count read from the device: the sum of cparts, by the
 // same tree in fp64 (whole numbers: exact in any order).  Count 0: the IEEE result.
 __global__ void __launch_bounds__(256) loss_from_parts_masked_kernel(const float* __restrict__ parts,
@@ -1276,14 +1203,6 @@ __global__ void __launch_bounds__(256) loss_from_parts_masked_kernel(const float
   }
 }
 
-int loss_from_parts_masked_launch(const float* parts, const float* cparts, int nparts, int kind, float* loss,
-                                  hipStream_t st) {
-  if (nparts < 1) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(loss_from_parts_masked_kernel, dim3(1), dim3(256), 0, st, parts, cparts, nparts, kind, loss);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // The upstream gradient of the masked loss from a finalised loss4, 0.0f where y or t is
 // not finite.  RMSE: (y - t) * loss[2], the fp32 expression tail_dgrad_kernel and
 // tail_wgrad_lds_kernel form on the fly.  MEAN: charb_partial_kernel's d / r * inv_count
@@ -1301,24 +1220,6 @@ __global__ void __launch_bounds__(256) loss_dy_masked_kernel(const float* __rest
     }
     dy[i] = g;
   }
-}
-
-int loss_dy_masked_launch(const float* y, const float* t, size_t n, int kind, float eps, const float* loss, float* dy,
-                          hipStream_t st) {
-  if (n < 1) return SRMI_ERR_SHAPE;
-  const size_t nblk = (n + 255) / 256;
-  hipLaunchKernelGGL(loss_dy_masked_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, y, t, n,
-                     kind, eps, loss, dy);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
-int batch_loss_means_launch(const float* sums, int ntiles, long long tile_elems, int bs, int kind, float* out,
-                            hipStream_t st) {
-  if (ntiles < 1 || tile_elems < 1 || bs < 1 || (ntiles + bs - 1) / bs > 1024) return SRMI_ERR_SHAPE;
-  hipLaunchKernelGGL(batch_loss_mean_kernel, dim3(1), dim3(256), 0, st, sums, ntiles, tile_elems, bs, kind, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // =============================================================== channel attention
@@ -1765,19 +1666,12 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
     adam_elem<true, EMA>(i, p, g, m, v, ema, b1, b2, eps, wd, step_size, bc2_sqrt, ema_decay, coef);
 }
 
-int adam_guarded_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, float b1, float b2,
-                        float eps, float wd, float step_size, float bc2_sqrt, float ema_decay, const float* ctl,
-                        hipStream_t st) {
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (ema)
-    hipLaunchKernelGGL(adam_guarded_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
-                       step_size, bc2_sqrt, ema_decay, ctl);
-  else
-    hipLaunchKernelGGL(adam_guarded_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
-                       step_size, bc2_sqrt, ema_decay, ctl);
-  SRMI_CHECK_LAUNCH();
-  return 0;
+// the bias corrections of step `step` (>= 1) in fp64: lr / (1 - b1^step) and sqrt(1 - b2^step)
+static void adam_corrections(int step, float lr, float b1, float b2, float* step_size, float* bc2_sqrt) {
+  const double bc1 = 1.0 - std::pow((double)b1, step);
+  const double bc2 = 1.0 - std::pow((double)b2, step);
+  *step_size = (float)(lr / bc1);
+  *bc2_sqrt = (float)std::sqrt(bc2);
 }
 
 // ------------------------------------------------------------------ gradient norm
@@ -1789,7 +1683,7 @@ int adam_guarded_launch(float* p, const float* g, float* m, float* v, float* ema
 // them in index order: no atomics, the partial count a function of n alone, the same bits
 // on every run (tile_loss_parts / loss_from_parts' convention).  A pure read: 16-byte loads
 // over the aligned middle of g, its up-to-3 head and tail elements by the first threads.
-size_t grad_norm_blocks(size_t n) {
+static size_t grad_norm_blocks(size_t n) {
   size_t blocks = (n + 255) / 256;
   return blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
 }
@@ -1846,26 +1740,6 @@ __global__ void __launch_bounds__(256) grad_norm_finalize_kernel(const double* _
     ctl[2] = finite ? 1.f : 0.f;
     ctl[3] = ctl[3] + (finite ? 0.f : 1.f);
   }
-}
-
-int grad_norm_launch(const float* g, size_t n, float max_norm, double* parts, float* ctl, hipStream_t st) {
-  const size_t blocks = grad_norm_blocks(n);
-  hipLaunchKernelGGL(grad_norm_parts_kernel, dim3(blocks), dim3(256), 0, st, g, n, parts);
-  SRMI_CHECK_LAUNCH();
-  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, parts, (int)blocks, max_norm, ctl);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
-int adam_launch(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                float wd, float step_size, float bc2_sqrt, hipStream_t st) {
-  (void)lr;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, b1, b2, eps, wd, step_size,
-                     bc2_sqrt);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // ========================================================================= packing
@@ -1999,13 +1873,207 @@ __global__ void pack_one_kernel(const float* __restrict__ W, const float* __rest
     pack_elem(W, B, Cout, Cin, ps, blockIdx.y, idx, fpack, dpack, pbias);
 }
 
-int pack_one_launch(const float* w, const float* b, int Cout, int Cin, int ps, void* fpack, void* dpack,
-                    float* pbias, int f32, hipStream_t st) {
+__global__ void scale_add_kernel(float* y, const float* x, float a, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    y[i] += a * x[i];
+}
+
+}  // namespace srmi
+
+using namespace srmi;
+
+extern "C" {
+
+int srmi_downsample(const float* hr, int N, int C, int H, int W, int scale, float* lr, void* stream) {
+  if (scale < 2 || H % scale || W % scale || N < 1 || C < 1) return SRMI_ERR_SHAPE;
+  const int plane = (H / scale) * (W / scale);
+  const int gy = N * C < kMaxGridY ? N * C : kMaxGridY;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(downsample_kernel, dim3((plane + 255) / 256, gy), dim3(256), 0, st, hr, N * C, H, W, scale, lr);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_upsample(const float* lr, int N, int C, int h, int w, int scale, float* hr, void* stream) {
+  if (scale < 1 || N < 1 || C < 1) return SRMI_ERR_SHAPE;
+  const int plane = h * scale * w * scale;
+  const int gy = N * C < kMaxGridY ? N * C : kMaxGridY;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(upsample_kernel, dim3((plane + 255) / 256, gy), dim3(256), 0, st, lr, N * C, h, w, scale, hr);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_interpolate(const float* x, int N, int C, int H, int W, int Ho, int Wo, float rh, float rw, int mode, float* y,
+                     void* stream) {
+  if (!x || !y || (mode != 1 && mode != 2)) return SRMI_ERR_ARG;
+  if (N < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || !(rh > 0.f) || !(rw > 0.f)) return SRMI_ERR_SHAPE;
+  const size_t tot = (size_t)N * C * Ho * Wo;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(interp_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, x, N * C, H, W, Ho, Wo, rh, rw, mode,
+                     y);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_rmse_finalize(float* loss4, void* stream) { return srmi_loss_finalize(loss4, SRMI_LOSS_RMSE, stream); }
+
+int srmi_loss_finalize(float* loss4, int kind, void* stream) {
+  if (!loss4 || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  return loss_finalize_launch(loss4, kind, static_cast<hipStream_t>(stream));
+}
+
+int srmi_loss_combine(float* loss, const float* parts, int nparts, int kind, void* stream) {
+  if (!loss || !parts || nparts < 1 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
+  hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), loss, parts, nparts,
+                     kind);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_batch_losses(const float* y, const float* t, int ntiles, long long tile_elems, int bs, int kind, float eps,
+                      float* work, float* out, void* stream) {
+  if (!y || !t || !work || !out || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  if (ntiles < 1 || tile_elems < 1 || bs < 1 || (ntiles + bs - 1) / bs > 1024) return SRMI_ERR_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (tile_elems % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)t & 15) == 0)
+    hipLaunchKernelGGL(tile_loss_sums_v4_kernel, dim3(ntiles), dim3(1024), 0, st, reinterpret_cast<const float4*>(y),
+                       reinterpret_cast<const float4*>(t), tile_elems / 4, kind, eps, work);
+  else
+    hipLaunchKernelGGL(tile_loss_sums_kernel, dim3(ntiles), dim3(256), 0, st, y, t, tile_elems, kind, eps, work);
+  SRMI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(batch_loss_mean_kernel, dim3(1), dim3(256), 0, st, work, ntiles, tile_elems, bs, kind, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tile_loss_parts(const float* y, const float* t, int ntiles, long long tile_elems, int kind, float eps,
+                         float* parts, void* stream) {
+  if (!y || !t || !parts || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  if (ntiles < 1 || tile_elems < 1) return SRMI_ERR_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tile_loss_parts_kernel, dim3(kTileSub, ntiles), dim3(256), 0, st, y, t, tile_elems, kind, eps,
+                     parts);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_loss_from_parts(const float* parts, int ntiles, double count, int kind, float* loss, void* stream) {
+  if (!parts || !loss || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
+  const int nparts = ntiles * kTileSub;
+  if (nparts < 1 || count <= 0) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(loss_from_parts_kernel, dim3(1), dim3(256), 0, st, parts, nparts, count, kind, loss);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tile_loss_parts_masked(const float* y, const float* t, int ntiles, long long tile_elems, int kind,
+                                float eps, float* parts, float* cparts, void* stream) {
+  if (!y || !t || !parts || !cparts || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  if (ntiles < 1 || tile_elems < 1) return SRMI_ERR_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tile_loss_parts_masked_kernel, dim3(kTileSub, ntiles), dim3(256), 0, st, y, t, tile_elems, kind,
+                     eps, parts, cparts);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_loss_from_parts_masked(const float* parts, const float* cparts, int ntiles, int kind, float* loss,
+                                void* stream) {
+  if (!parts || !cparts || !loss || ntiles < 1 || kind < -1 || kind > SRMI_LOSS_MEAN) return SRMI_ERR_ARG;
+  const int nparts = ntiles * kTileSub;
+  if (nparts < 1) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(loss_from_parts_masked_kernel, dim3(1), dim3(256), 0, st, parts, cparts, nparts, kind, loss);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_loss_dy_masked(const float* y, const float* t, size_t n, int kind, float eps, const float* loss, float* dy,
+                        void* stream) {
+  if (!y || !t || !loss || !dy || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  if (n < 1) return SRMI_ERR_SHAPE;
+  const size_t nblk = (n + 255) / 256;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(loss_dy_masked_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, y, t, n,
+                     kind, eps, loss, dy);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_batch_loss_means(const float* sums, int ntiles, long long tile_elems, int bs, int kind, float* out,
+                          void* stream) {
+  if (!sums || !out || (kind != SRMI_LOSS_RMSE && kind != SRMI_LOSS_MEAN)) return SRMI_ERR_ARG;
+  if (ntiles < 1 || tile_elems < 1 || bs < 1 || (ntiles + bs - 1) / bs > 1024) return SRMI_ERR_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(batch_loss_mean_kernel, dim3(1), dim3(256), 0, st, sums, ntiles, tile_elems, bs, kind, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_adam_step(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float b1, float b2,
+                   float eps, float wd, void* stream) {
+  if (step < 1) return SRMI_ERR_ARG;
+  float step_size, bc2_sqrt;
+  adam_corrections(step, lr, b1, b2, &step_size, &bc2_sqrt);
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, b1, b2, eps, wd, step_size,
+                     bc2_sqrt);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_adam_step_guarded(float* p, const float* g, float* m, float* v, float* ema, size_t n, int step, float lr,
+                           float b1, float b2, float eps, float wd, float ema_decay, const float* ctl, void* stream) {
+  if (step < 1 || !ctl) return SRMI_ERR_ARG;
+  if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return SRMI_ERR_ARG;
+  float step_size, bc2_sqrt;
+  adam_corrections(step, lr, b1, b2, &step_size, &bc2_sqrt);
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (ema)
+    hipLaunchKernelGGL(adam_guarded_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
+                       step_size, bc2_sqrt, ema_decay, ctl);
+  else
+    hipLaunchKernelGGL(adam_guarded_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, b1, b2, eps, wd,
+                       step_size, bc2_sqrt, ema_decay, ctl);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_grad_norm_workspace(size_t n, size_t* bytes) {
+  if (!bytes || n < 1) return SRMI_ERR_ARG;
+  *bytes = grad_norm_blocks(n) * sizeof(double);
+  return 0;
+}
+
+int srmi_grad_norm(const float* g, size_t n, float max_norm, void* workspace, size_t ws_bytes, float* ctl,
+                   void* stream) {
+  if (!g || !workspace || !ctl || n < 1 || !(max_norm > 0.f)) return SRMI_ERR_ARG;  // (a NaN max_norm too)
+  const size_t blocks = grad_norm_blocks(n);
+  if (ws_bytes < blocks * sizeof(double) || ((size_t)workspace & 7) || ((size_t)g & 3)) return SRMI_ERR_ARG;
+  double* parts = (double*)workspace;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(grad_norm_parts_kernel, dim3(blocks), dim3(256), 0, st, g, n, parts);
+  SRMI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, parts, (int)blocks, max_norm, ctl);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_pack_conv(const float* w, const float* b, int Cout, int Cin, int ps, void* fpack, void* dpack, float* pbias,
+                   int dtype, void* stream) {
+  if (dtype != SRMI_DTYPE_BF16 && dtype != SRMI_DTYPE_F32) return SRMI_ERR_ARG;
   if (Cout % 64 || Cin % 64) return SRMI_ERR_SHAPE;
   if (ps && Cout != 256) return SRMI_ERR_SHAPE;  // the PixelShuffle(2) permutation spans 4 x 64 channels
   long long bx = ((long long)Cout * Cin * 9 + 255) / 256;
   if (bx > 1024) bx = 1024;
-  if (f32)
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == SRMI_DTYPE_F32)
     hipLaunchKernelGGL(pack_one_kernel<float>, dim3((unsigned)bx, 3), dim3(256), 0, st, w, b, Cout, Cin, ps,
                        static_cast<float*>(fpack), static_cast<float*>(dpack), pbias);
   else
@@ -2015,17 +2083,14 @@ int pack_one_launch(const float* w, const float* b, int Cout, int Cin, int ps, v
   return 0;
 }
 
-__global__ void scale_add_kernel(float* y, const float* x, float a, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    y[i] += a * x[i];
-}
-
-int scale_add_launch(float* y, const float* x, float a, size_t n, hipStream_t st) {
+int srmi_axpy(float* y, const float* x, float a, size_t n, void* stream) {
+  if (!y || !x) return SRMI_ERR_ARG;
   size_t blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(scale_add_kernel, dim3(blocks), dim3(256), 0, st, y, x, a, n);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -341,8 +341,13 @@ int spec_plan(int C, int H, int W, int P, int Q, SpecPlan* p) {
 }
 
 }  // namespace
+}  // namespace srmi
 
-int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes) {
   SpecPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = spec_plan(C, H, W, P, Q, &p);
@@ -351,8 +356,8 @@ int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes) {
   return 0;
 }
 
-int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
-                   float* out, int* nused, hipStream_t st) {
+int srmi_spectra(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
+                 float* out, int* nused, void* stream) {
   SpecPlan p;
   if (!a || !b || !ws || !out || !nused || ((uintptr_t)ws & 15) != 0) return SRMI_ERR_ARG;
   const int rc = spec_plan(C, H, W, P, Q, &p);
@@ -361,6 +366,7 @@ int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, i
   int* skip = static_cast<int*>(ws);
   double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + p.off_partial);
   float2* scratch = reinterpret_cast<float2*>(static_cast<char*>(ws) + p.off_scratch);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(spectra_flags_kernel, dim3(p.nwin), dim3(kSpecThreads), 0, st, a, b, C, H, W, P, Q, p.nx, skip);
   SRMI_CHECK_LAUNCH();
 #define SRMI_SPEC_CASE(PP)                                                                                         \
@@ -386,4 +392,4 @@ int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, i
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

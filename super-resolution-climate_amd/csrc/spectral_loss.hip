@@ -343,8 +343,13 @@ __global__ void __launch_bounds__(kSpecThreads) spectral_loss_dy_kernel(const ch
 }
 
 }  // namespace
+}  // namespace srmi
 
-int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes) {
   SpecLossPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = spec_loss_plan(nplanes, H, W, P, Q, &p);
@@ -353,8 +358,8 @@ int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_
   return 0;
 }
 
-int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
-                               float eps, float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st) {
+int srmi_spectral_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
+                             float eps, float* parts, float* cparts, void* ws, size_t ws_bytes, void* stream) {
   SpecLossPlan p;
   if (!pred || !target || !parts || !cparts || !ws || ((uintptr_t)ws & 15) != 0 || !(eps > 0.0f) || !std::isfinite(eps))
     return SRMI_ERR_ARG;
@@ -364,6 +369,7 @@ int spectral_loss_parts_launch(const float* pred, const float* target, long long
   const long long nunits = nplanes * ((p.nwin + 1) / 2);
   const int grid = (int)(nunits < kSpecLossGridCap ? nunits : kSpecLossGridCap);
   char* w = static_cast<char*>(ws);
+  hipStream_t st = static_cast<hipStream_t>(stream);
 #define SRMI_SPEC_LOSS_CASE(PP)                                                                               \
   case PP:                                                                                                    \
     hipLaunchKernelGGL(spectral_loss_window_kernel<PP>, dim3(grid), dim3(kSpecThreads), 0, st, pred, target, \
@@ -384,19 +390,20 @@ int spectral_loss_parts_launch(const float* pred, const float* target, long long
   return 0;
 }
 
-int spectral_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, int P, float weight,
-                                    const float* loss4, float* spec4, float* total, hipStream_t st) {
+int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
+                                  const float* loss4, float* spec4, float* total, void* stream) {
   if (!parts || !cparts || !loss4 || !spec4 || !total || nplanes < 1 || (P != 16 && P != 32 && P != 64) ||
       !(weight >= 0.0f) || !std::isfinite(weight))
     return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(spectral_loss_finalize_kernel, dim3(1), dim3(kSpecThreads), 0, st, parts, cparts, nplanes, P,
                      weight, loss4, spec4, total);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-int spectral_loss_dy_launch(const void* ws, size_t ws_bytes, long long nplanes, int H, int W, int P, int Q,
-                            float weight, const float* spec4, float* dy, hipStream_t st) {
+int srmi_spectral_loss_dy(const void* ws, size_t ws_bytes, long long nplanes, int H, int W, int P, int Q,
+                          float weight, const float* spec4, float* dy, void* stream) {
   SpecLossPlan p;
   if (!ws || ((uintptr_t)ws & 15) != 0 || !spec4 || !dy || !(weight >= 0.0f) || !std::isfinite(weight)) return SRMI_ERR_ARG;
   const int rc = spec_loss_plan(nplanes, H, W, P, Q, &p);
@@ -406,10 +413,11 @@ int spectral_loss_dy_launch(const void* ws, size_t ws_bytes, long long nplanes, 
   const long long npix = nplanes * H * (long long)W;
   const long long blocks = (npix + kSpecThreads - 1) / kSpecThreads;
   const int grid = (int)(blocks < kSpecLossDyGridCap ? blocks : kSpecLossDyGridCap);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(spectral_loss_dy_kernel, dim3(grid), dim3(kSpecThreads), 0, st, static_cast<const char*>(ws), p,
                      npix, H, W, P, Q, weight, spec4, dy);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -116,7 +116,6 @@ struct ConvParams {
   CaBwdIn gx;
 };
 
-void conv3x3_set_debug_stamps(unsigned long long* buf);
 unsigned long long* conv3x3_debug_stamps();  // (null unless a diagnostic run set it)
 unsigned long long* conv3x3_stamps_for(int epi);  // (diagnostic build: SRMI_STAMP_EPI selects one epilogue)
 int conv3x3_launch(const ConvParams& p, int epi, hipStream_t st);  // dispatches p.f32
@@ -153,7 +152,6 @@ struct WgradParams {
   // from it in LDS, as ConvParams.gx
   CaBwdIn gx;
 };
-void wgrad3x3_set_debug_stamps(unsigned long long* buf);
 int wgrad3x3_launch(const WgradParams& p, hipStream_t st);  // dispatches p.f32
 int wgrad_f32_launch(const WgradParams& p, hipStream_t st);
 int wgrad3x3_nslabs(const WgradParams& p);
@@ -172,7 +170,7 @@ int wgrad_reduce_sets_launch(const ReduceSet* sets, int n, hipStream_t st);
 int rcab_bwd_fusable(const ConvParams& cp, const WgradParams& wp);
 int rcab_bwd_launch(const ConvParams& cp, int epi, int conv_cus, const WgradParams& wp, hipStream_t st);
 
-// small-channel kernels (head / tail), bicubic resampling, loss, CA, Adam, packing
+// small-channel kernels (head / tail), loss, CA, packing (small.hip)
 // f32 != 0: the operand-type outputs / inputs below are fp32 (exact-fp32 engine mode)
 int head_fwd_launch(const float* lr, const float* w, const float* b, int N, int C, int H, int W, float* x0f,
                     void* x0b, int f32, hipStream_t st);
@@ -189,10 +187,6 @@ int tail_wgrad_launch(const float* y, const float* hr, const float* loss, const 
                       int W, float* slab, int* nslab, int f32, hipStream_t st);
 int tail_wgrad_reduce_launch(const float* slab, int nslab, int C, float* gw, float* gb, hipStream_t st);
 
-int downsample_launch(const float* hr, int N, int C, int H, int W, int scale, float* lr, hipStream_t st);
-int upsample_launch(const float* lr, int N, int C, int h, int w, int scale, float* hr, hipStream_t st);
-int interp_launch(const float* x, int N, int C, int H, int W, int Ho, int Wo, float rh, float rw, int mode, float* y,
-                  hipStream_t st);
 // loss[0] = sum (y-t)^2 (this rank), loss[1] = element count (global after all-reduce)
 int sqerr_partial_launch(const float* y, const float* t, size_t n, float* partial, int nblk, hipStream_t st);
 int sqerr_finish_launch(const float* partial, int nblk, double count, float* loss, hipStream_t st);
@@ -201,28 +195,8 @@ int sqerr_finish_launch(const float* partial, int nblk, double count, float* los
 int sqerr_masked_launch(const float* y, const float* t, size_t n, double* partial, int nblk, float* loss,
                         hipStream_t st);
 enum LossKind { LOSS_RMSE = 0, LOSS_MEAN = 1 };
-int loss_finalize_launch(float* loss, int kind, hipStream_t st);
-int loss_combine_launch(float* loss, const float* parts, int nparts, int kind, hipStream_t st);
-int batch_losses_launch(const float* y, const float* t, int ntiles, long long tile_elems, int bs, int kind, float eps,
-                        float* work, float* out, hipStream_t st);
-int batch_loss_means_launch(const float* sums, int ntiles, long long tile_elems, int bs, int kind, float* out,
-                            hipStream_t st);
-// split-invariant loss sums (small.hip): parts[tile][kTileSub] of every tile, then S in
-// fixed order (fp64) into loss4, finalised as kind (>= 0)
-constexpr int kTileSub = 16;
-int tile_loss_parts_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind, float eps,
-                           float* parts, hipStream_t st);
-int loss_from_parts_launch(const float* parts, int nparts, double count, int kind, float* loss, hipStream_t st);
 int charb_partial_launch(const float* y, const float* t, size_t n, float eps, double count, float* dy,
                          float* partial, int nblk, hipStream_t st);
-// the same over the elements where y and t are both finite (training on tiles with land):
-// the count rides in cparts and is summed on the device; dy from the finalised loss
-int tile_loss_parts_masked_launch(const float* y, const float* t, int ntiles, long long tile_elems, int kind,
-                                  float eps, float* parts, float* cparts, hipStream_t st);
-int loss_from_parts_masked_launch(const float* parts, const float* cparts, int nparts, int kind, float* loss,
-                                  hipStream_t st);
-int loss_dy_masked_launch(const float* y, const float* t, size_t n, int kind, float eps, const float* loss, float* dy,
-                          hipStream_t st);
 
 // channel attention
 // residual stream: fp32 h_in / h_out, or (bf16 engine) as a bf16 hi + lo pair: lo_out
@@ -245,18 +219,6 @@ int rcab_infer_launch(const ConvParams& c1, const ConvParams& c2, const float* p
 int ca_param_grads_batched_launch(const float* recs, const float* brecs, int nblocks, int N, size_t rstride,
                                   size_t bstride, int C, int R, const long long* offs, float* grads, hipStream_t st);
 
-int adam_launch(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                float wd, float step_size, float bc2_sqrt, hipStream_t st);
-// adam_launch's step on g * ctl[1], skipped whole when ctl[2] == 0; ema (may be null):
-// ema += (1 - ema_decay) (p' - ema) in the same pass
-int adam_guarded_launch(float* p, const float* g, float* m, float* v, float* ema, size_t n, float b1, float b2,
-                        float eps, float wd, float step_size, float bc2_sqrt, float ema_decay, const float* ctl,
-                        hipStream_t st);
-// the L2 norm of g in fp64, fixed order: grad_norm_blocks(n) partials, then ctl[4] =
-// (norm, clip coefficient, finite, running count of non-finite norms)
-size_t grad_norm_blocks(size_t n);
-int grad_norm_launch(const float* g, size_t n, float max_norm, double* parts, float* ctl, hipStream_t st);
-
 struct PackEntry {
   long long w_off;   // offset of the fp32 weight [Cout][Cin][3][3] in the param buffer
   long long b_off;   // offset of the fp32 bias [Cout]
@@ -269,106 +231,7 @@ struct PackEntry {
 int pack_launch(const float* params, const PackEntry* dev_entries, int nentries, int max_cob, int max_cib,
                 void* packs, float* pbias, int f32, hipStream_t st);
 
-int pack_one_launch(const float* w, const float* b, int Cout, int Cin, int ps, void* fpack, void* dpack,
-                    float* pbias, int f32, hipStream_t st);
-
-int scale_add_launch(float* y, const float* x, float a, size_t n, hipStream_t st);
-
-// tiled-region data path (tiles.hip)
-int region_to_tiles_launch(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
-                           float* stdv, int* bad, hipStream_t st);
-int tiles_to_region_launch(const float* tiles, const float* mean, const float* stdv, const int* inv, int C, int ty,
-                           int tx, int gy, int gx, float* out, hipStream_t st);
-int llc_index_map_workspace(long long n, size_t* bytes);
-int llc_index_map_launch(const uint32_t* tmpl, long long n, int nx, int y0, int ys, int x0, int xs, int* idx,
-                         long long* n_wet, void* ws, size_t ws_bytes, hipStream_t st);
-int llc_gather_launch(const uint32_t* data, long long nvals, const int* idx, long long np, float* out,
-                      hipStream_t st);
-int tiles_nonfinite_launch(const float* region, int C, int H, int W, int ty, int tx, int* bad, hipStream_t st);
-int tiles_gather_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
-                        float* out, hipStream_t st);
-// sparse file reads and the device keep list of the time-slice feed (tiles.hip)
-int llc_block_mask_launch(const int* idx, long long np, int shift, int* mask, int n_blocks, hipStream_t st);
-int llc_compact_map_launch(const int* idx, long long np, int shift, const int* base, int n_blocks, int* out,
-                           hipStream_t st);
-int tiles_keep_launch(const int* bad, int C, int ncells, int* src, int* count, hipStream_t st);
-int tiles_gather_dev_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src,
-                            const int* count, int max_slots, float* out, hipStream_t st);
-int batch_prep_launch(const float* raw, int B, int C, int T, int flip, int scale, float* hr, float* lr, float* mean,
-                      float* stdv, hipStream_t st);
-// the other task.norm modes and the dataset tile statistics (tiles.hip)
-int batch_prep_norm_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
-                           const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
-                           hipStream_t st);
-int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
-                                const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
-                                hipStream_t st);
-// overlapped tiles and their blended mosaic (tiles.hip)
+// tiles along an axis of an overlapped cut (tiles.hip; the spectral files plan with it)
 int overlap_count(long long L, long long t, long long S);
-int region_to_tiles_overlap_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
-                                   const float* off, const float* dv, float* tiles, float* off_out, float* div_out,
-                                   int* bad, hipStream_t st);
-int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
-                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st);
-// the land-aware forms: masked cut with a fill, re-masking blend (tiles.hip)
-int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
-                                          int mode, const float* off, const float* dv, float* tiles, float* off_out,
-                                          float* div_out, int* bad, int min_wet, int* nwet, hipStream_t st);
-int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
-                              int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
-                              hipStream_t st);
-// geometric self-ensemble: the dihedral variants of tile planes, the blend of their outputs (tiles.hip)
-int tiles_dihedral_launch(const float* in, long long nplanes, int h, int w, int variants, float* out, hipStream_t st);
-int tiles_blend_ensemble_launch(const float* tiles, int variants, const float* off, const float* dv, const int* bad,
-                                int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src,
-                                int scale, float* mean, float* spread, hipStream_t st);
-// land in training: the keep flags with a threshold, the fill in place, the masked prep
-int tiles_dry_launch(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
-                     hipStream_t st);
-int tiles_fill_launch(float* tiles, long long nplanes, int h, int w, int* passes, hipStream_t st);
-int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
-                             const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
-                             int* nwet, hipStream_t st);
-// the spectral score: windowed radial power spectra of two fields (spectra.hip)
-int spectra_workspace(int C, int H, int W, int P, int Q, size_t* bytes);
-int spectra_launch(const float* a, const float* b, int C, int H, int W, int P, int Q, void* ws, size_t ws_bytes,
-                   float* out, int* nused, hipStream_t st);
-// the SSIM / PSNR score: Gaussian-window structural similarity of two fields (ssim.hip)
-int ssim_workspace(int C, int H, int W, size_t* bytes);
-int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_range, void* ws, size_t ws_bytes,
-                float* out, long long* count, float* map, hipStream_t st);
-// the distribution score: histograms, joint histogram and quantiles of two fields (distribution.hip)
-int distribution_workspace(int C, int H, int W, int nbins, int njoint, size_t* bytes);
-int distribution_launch(const float* a, const float* b, int C, int H, int W, int nbins, int njoint, const float* lo_hi,
-                        const double* probs, int nprobs, void* ws, size_t ws_bytes, long long* hist, long long* joint,
-                        float* range, long long* count, double* derived, int flags, hipStream_t st);
-// the quantile map: accumulated histograms, the transfer table, the mapped field (quantile_map.hip)
-int quantile_map_accumulate_workspace(int C, int H, int W, int nbins, size_t* bytes);
-int quantile_map_accumulate_launch(const float* src, const float* truth, const float* base, int C, int H, int W,
-                                   int nbins, const float* range, int first, void* ws, size_t ws_bytes,
-                                   long long* hist, long long* count, hipStream_t st);
-int quantile_map_fit_launch(const long long* hist, const long long* count, int C, int nbins, const float* range,
-                            long long tail_count, double* knots, float* table, float* meta, hipStream_t st);
-int quantile_map_apply_launch(const float* x, const float* base, int C, int H, int W, int nbins, const float* table,
-                              const float* meta, float strength, float* out, hipStream_t st);
-// the spectral loss term of the training step (spectral_loss.hip)
-int spectral_loss_workspace(long long nplanes, int H, int W, int P, int Q, size_t* bytes);
-int spectral_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, int P, int Q,
-                               float eps, float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st);
-int spectral_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, int P, float weight,
-                                    const float* loss4, float* spec4, float* total, hipStream_t st);
-int spectral_loss_dy_launch(const void* ws, size_t ws_bytes, long long nplanes, int H, int W, int P, int Q,
-                            float weight, const float* spec4, float* dy, hipStream_t st);
-// the SSIM loss term of the training step (ssim_loss.hip)
-int ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes);
-int ssim_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
-                           float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st);
-int ssim_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, float weight,
-                                const float* base, float* ssim4, float* total, hipStream_t st);
-int ssim_loss_dy_launch(const void* ws, size_t ws_bytes, const float* pred, const float* target, long long nplanes,
-                        int H, int W, float weight, const float* ssim4, float* dy, hipStream_t st);
-int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, hipStream_t st);
-int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
-                               hipStream_t st);
 
 }  // namespace srmi

@@ -241,8 +241,13 @@ int ssim_plan(int C, int H, int W, SsimPlan* p) {
 }
 
 }  // namespace
+}  // namespace srmi
 
-int ssim_workspace(int C, int H, int W, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_ssim_workspace(int C, int H, int W, size_t* bytes) {
   SsimPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = ssim_plan(C, H, W, &p);
@@ -251,8 +256,8 @@ int ssim_workspace(int C, int H, int W, size_t* bytes) {
   return 0;
 }
 
-int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_range, void* ws, size_t ws_bytes,
-                float* out, long long* count, float* map, hipStream_t st) {
+int srmi_ssim(const float* a, const float* b, int C, int H, int W, float data_range, void* ws, size_t ws_bytes,
+              float* out, long long* count, float* map, void* stream) {
   SsimPlan p;
   if (!a || !b || !ws || !out || !count || ((uintptr_t)ws & 15) != 0 || !std::isfinite(data_range)) return SRMI_ERR_ARG;
   const int rc = ssim_plan(C, H, W, &p);
@@ -265,6 +270,7 @@ int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_
   float* lout = reinterpret_cast<float*>(base + p.off_l);
   SsimTaps taps;
   ssim_fill_taps(&taps);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ssim_minmax_kernel, dim3(p.nblk, C), dim3(kSsimThreads), 0, st, b, (long long)H * W, p.nblk, mm);
   SRMI_CHECK_LAUNCH();
   hipLaunchKernelGGL(ssim_tile_kernel, dim3((unsigned)p.ntiles), dim3(kSsimThreads), 0, st, a, b, H, W, p.tiles_x,
@@ -276,4 +282,4 @@ int ssim_launch(const float* a, const float* b, int C, int H, int W, float data_
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

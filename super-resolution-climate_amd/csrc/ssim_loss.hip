@@ -372,8 +372,13 @@ __global__ void __launch_bounds__(kSsimThreads, 2) ssim_loss_dy_kernel(const cha
 bool bad_weight(float w) { return !(w >= 0.0f) || !std::isfinite(w); }
 
 }  // namespace
+}  // namespace srmi
 
-int ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes) {
+using namespace srmi;
+
+extern "C" {
+
+int srmi_ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes) {
   SsimLossPlan p;
   if (!bytes) return SRMI_ERR_ARG;
   const int rc = ssim_loss_plan(nplanes, H, W, &p);
@@ -382,8 +387,8 @@ int ssim_loss_workspace(long long nplanes, int H, int W, size_t* bytes) {
   return 0;
 }
 
-int ssim_loss_parts_launch(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
-                           float* parts, float* cparts, void* ws, size_t ws_bytes, hipStream_t st) {
+int srmi_ssim_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, float data_range,
+                         float* parts, float* cparts, void* ws, size_t ws_bytes, void* stream) {
   SsimLossPlan p;
   if (!pred || !target || !parts || !cparts || !ws || ((uintptr_t)ws & 15) != 0 || !std::isfinite(data_range))
     return SRMI_ERR_ARG;
@@ -393,6 +398,7 @@ int ssim_loss_parts_launch(const float* pred, const float* target, long long npl
   char* w = static_cast<char*>(ws);
   SsimTaps taps;
   ssim_fill_taps(&taps);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ssim_loss_minmax_kernel, dim3((unsigned)(nplanes * p.nblk)), dim3(kSsimThreads), 0, st, target,
                      H * W, p.nblk, w, p);
   SRMI_CHECK_LAUNCH();
@@ -404,17 +410,18 @@ int ssim_loss_parts_launch(const float* pred, const float* target, long long npl
   return 0;
 }
 
-int ssim_loss_from_parts_launch(const float* parts, const float* cparts, long long nplanes, float weight,
-                                const float* base, float* ssim4, float* total, hipStream_t st) {
+int srmi_ssim_loss_from_parts(const float* parts, const float* cparts, long long nplanes, float weight,
+                              const float* base, float* ssim4, float* total, void* stream) {
   if (!parts || !cparts || !base || !ssim4 || !total || nplanes < 1 || bad_weight(weight)) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ssim_loss_finalize_kernel, dim3(1), dim3(kSsimThreads), 0, st, parts, cparts, nplanes, weight,
                      base, ssim4, total);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-int ssim_loss_dy_launch(const void* ws, size_t ws_bytes, const float* pred, const float* target, long long nplanes,
-                        int H, int W, float weight, const float* ssim4, float* dy, hipStream_t st) {
+int srmi_ssim_loss_dy(const void* ws, size_t ws_bytes, const float* pred, const float* target, long long nplanes,
+                      int H, int W, float weight, const float* ssim4, float* dy, void* stream) {
   SsimLossPlan p;
   if (!ws || ((uintptr_t)ws & 15) != 0 || !pred || !target || !ssim4 || !dy || bad_weight(weight)) return SRMI_ERR_ARG;
   const int rc = ssim_loss_plan(nplanes, H, W, &p);
@@ -423,10 +430,11 @@ int ssim_loss_dy_launch(const void* ws, size_t ws_bytes, const float* pred, cons
   if (weight == 0.0f) return 0;  // dy stays as it is, bit for bit
   SsimTaps taps;
   ssim_fill_taps(&taps);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ssim_loss_dy_kernel, dim3((unsigned)(nplanes * p.dtiles_per_plane)), dim3(kSsimThreads), 0, st,
                      static_cast<const char*>(ws), p, pred, target, H, W, weight, taps, ssim4, dy);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -168,12 +168,6 @@ static int region_to_tiles_plan_launch(const float* region, int C, int H, int W,
   return 0;
 }
 
-int region_to_tiles_launch(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
-                           float* stdv, int* bad, hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
-  return region_to_tiles_plan_launch(region, C, H, W, ty, tx, H / ty, W / tx, ty, tx, tiles, mean, stdv, bad, st);
-}
-
 // out[c][Y][X] = tiles[inv[cell]][c][y][x] * std + mean, NaN where inv[cell] < 0
 // (inv == NULL: tile i is grid cell i).  grid (ceil(gx*tx / 256), gy*ty, C)
 __global__ void __launch_bounds__(256) tiles_to_region_kernel(const float* __restrict__ tiles,
@@ -216,21 +210,6 @@ __global__ void __launch_bounds__(256) tiles_to_region_v4_kernel(const float* __
     }
   }
   *reinterpret_cast<float4*>(out + ((size_t)c * gridDim.y + Y) * Wo + X) = v;
-}
-
-int tiles_to_region_launch(const float* tiles, const float* mean, const float* stdv, const int* inv, int C, int ty,
-                           int tx, int gy, int gx, float* out, hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || gy < 1 || gx < 1) return SRMI_ERR_SHAPE;
-  if (tx % 4 == 0 && ((uintptr_t)tiles & 15) == 0 && ((uintptr_t)out & 15) == 0) {
-    hipLaunchKernelGGL(tiles_to_region_v4_kernel, dim3((gx * tx / 4 + 255) / 256, gy * ty, C), dim3(256), 0, st,
-                       tiles, mean, stdv, inv, C, ty, tx, gx, out);
-    SRMI_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(tiles_to_region_kernel, dim3((gx * tx + 255) / 256, gy * ty, C), dim3(256), 0, st, tiles, mean,
-                     stdv, inv, C, ty, tx, gx, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // ------------------------------------------------------------------ batch prep
@@ -350,23 +329,6 @@ __global__ void __launch_bounds__(kPrepThreads) batch_prep_kernel(const float* _
     if (mean) mean[(size_t)b * C + c] = (float)m;
     if (stdv) stdv[(size_t)b * C + c] = (float)sd;
   }
-}
-
-int batch_prep_launch(const float* raw, int B, int C, int T, int flip, int scale, float* hr, float* lr, float* mean,
-                      float* stdv, hipStream_t st) {
-  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7) return SRMI_ERR_SHAPE;
-  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
-  if (!raw || !hr) return SRMI_ERR_ARG;
-  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
-  if (lds <= 150 * 1024) {
-    hipLaunchKernelGGL(batch_prep_kernel<true>, dim3(C, B), dim3(kPrepThreads), lds, st, raw, C, T, flip, scale, hr,
-                       lr, mean, stdv);
-  } else {
-    hipLaunchKernelGGL(batch_prep_kernel<false>, dim3(C, B), dim3(kPrepThreads), 0, st, raw, C, T, flip, scale, hr,
-                       lr, mean, stdv);
-  }
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // ------------------------------------------------- the other task.norm modes
@@ -493,36 +455,6 @@ __global__ void __launch_bounds__(kPrepThreads) batch_prep_norm_kernel(const flo
   }
 }
 
-int batch_prep_norm_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
-                           const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
-                           hipStream_t st) {
-  if (mode == SRMI_NORM_LNORM) {
-    if (B > 65535) return SRMI_ERR_SHAPE;  // batch_prep_launch's grid.y
-    return batch_prep_launch(raw, (int)B, C, T, flip, scale, hr, lr, off_out, div_out, st);
-  }
-  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
-  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
-  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
-  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
-  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
-  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
-  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
-  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
-#define SRMI_PREP_NORM(LDS, MODE, BYTES)                                                                          \
-  hipLaunchKernelGGL((batch_prep_norm_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
-                     lr, off_out, div_out)
-  if (lds <= 150 * 1024) {
-    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(true, SRMI_NORM_LSCALE, lds);
-    else SRMI_PREP_NORM(true, SRMI_NORM_AFFINE, lds);
-  } else {
-    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(false, SRMI_NORM_LSCALE, 0);
-    else SRMI_PREP_NORM(false, SRMI_NORM_AFFINE, 0);
-  }
-#undef SRMI_PREP_NORM
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // float4s a thread of the register-resident forms below holds: a 192^2 plane over 1024
 // threads (12, as region_to_tiles_reg_kernel, spills next to their fp64 arithmetic)
 constexpr int kNormKR = 9;
@@ -626,22 +558,6 @@ static int region_to_tiles_norm_plan_launch(const float* region, int C, int H, i
   return 0;
 }
 
-int region_to_tiles_norm_launch(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
-                                const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
-                                hipStream_t st) {
-  if (mode == SRMI_NORM_LNORM) {
-    if (!region || !tiles || !off_out || !div_out) return SRMI_ERR_ARG;
-    return region_to_tiles_launch(region, C, H, W, ty, tx, tiles, off_out, div_out, bad, st);
-  }
-  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
-  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
-  const int gy = H / ty, gx = W / tx;
-  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
-  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, ty, tx, mode, off, dv, tiles, off_out,
-                                          div_out, bad, st);
-}
-
 // ------------------------------------------------ overlapped tiles, blended mosaic
 // No reference counterpart: get_tiles (raw.py:216-233) cuts the disjoint floor grid and
 // assemble_images (dual_trainer.py:482-512) concatenates it.  Here an axis of length L
@@ -653,23 +569,6 @@ int overlap_count(long long L, long long t, long long S) {
   if (S < 1 || t < S || L < t || L > 0x7fffffffLL) return SRMI_ERR_ARG;
   const long long n = (L - t + S - 1) / S + 1;
   return n > 0x7fffffffLL ? SRMI_ERR_ARG : (int)n;
-}
-
-int region_to_tiles_overlap_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
-                                   const float* off, const float* dv, float* tiles, float* off_out, float* div_out,
-                                   int* bad, hipStream_t st) {
-  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
-  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.x
-  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
-  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
-  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
-  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
-      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
-    return SRMI_ERR_ARG;
-  if (mode == SRMI_NORM_LNORM)
-    return region_to_tiles_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, tiles, off_out, div_out, bad, st);
-  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, mode, off, dv, tiles, off_out,
-                                          div_out, bad, st);
 }
 
 // the tiles i with origin(i) <= p < origin(i) + t are lo .. hi, without a gap: tiles
@@ -798,18 +697,6 @@ static int tiles_blend_any_launch(const float* tiles, const float* off, const fl
   return 0;
 }
 
-int tiles_blend_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
-                       int Sy, int Sx, int Ho, int Wo, float* out, hipStream_t st) {
-  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, nullptr, 1, out, st);
-}
-
-int tiles_blend_masked_launch(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
-                              int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
-                              hipStream_t st) {
-  if (!mask_src || scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale) return SRMI_ERR_ARG;
-  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out, st);
-}
-
 // ------------------------------------------------ geometric self-ensemble (the "+" variant)
 // No reference counterpart.  The model runs on the dihedral variants of every tile --
 // variant f is xyflip's (flip_src above: bit 0 flips x, bit 1 flips y, bit 2 swaps the
@@ -880,23 +767,6 @@ __global__ void __launch_bounds__(256) tiles_dihedral_kernel(const float* __rest
       }
     }
   }
-}
-
-int tiles_dihedral_launch(const float* in, long long nplanes, int h, int w, int variants, float* out,
-                          hipStream_t st) {
-  if (variants < 1 || variants > 255 || !in || !out || in == out) return SRMI_ERR_ARG;
-  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
-  if ((variants & 0xf0) && h != w) return SRMI_ERR_SHAPE;  // a swap of a rectangular plane
-  const int nby = (h + kDihB - 1) / kDihB, nbx = (w + kDihB - 1) / kDihB;
-  if (nplanes * nby * nbx > 0x7fffffffLL) return SRMI_ERR_SHAPE;  // grid.x
-  const size_t slab = (size_t)nplanes * h * w;
-  const dim3 grid((unsigned)(nplanes * nby * nbx));
-  if (w % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
-    hipLaunchKernelGGL(tiles_dihedral_kernel<true>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
-  else
-    hipLaunchKernelGGL(tiles_dihedral_kernel<false>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // kV values of slab `s` ([Ty][Tx], stored in variant f's frame) at tile-local (qy, qx ..
@@ -1057,38 +927,6 @@ __global__ void __launch_bounds__(256) tiles_blend_ensemble_kernel(
   }
 }
 
-int tiles_blend_ensemble_launch(const float* tiles, int variants, const float* off, const float* dv, const int* bad,
-                                int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src,
-                                int scale, float* mean, float* spread, hipStream_t st) {
-  if (variants < 1 || variants > 255) return SRMI_ERR_ARG;
-  if (mask_src && (scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale)) return SRMI_ERR_ARG;
-  // from here as tiles_blend_any_launch
-  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.z
-  const int ny = overlap_count(Ho, Ty, Sy), nx = overlap_count(Wo, Tx, Sx);
-  if (ny < 0 || nx < 0) return SRMI_ERR_ARG;
-  const long long wy = (long long)(Ty / Sy + 2) * (Ty - Sy + 1), wx = (long long)(Tx / Sx + 2) * (Tx - Sx + 1);
-  if (Ho > 65535 || (long long)ny * nx > 0x7fffffffLL || wy * wx > 0x7fffffffLL) return SRMI_ERR_SHAPE;
-  if ((variants & 0xf0) && Ty != Tx) return SRMI_ERR_SHAPE;  // a swap of a rectangular tile
-  if (!tiles || !mean || (off && !dv)) return SRMI_ERR_ARG;
-  const int K = __builtin_popcount((unsigned)variants);
-  const bool vec = Tx % 4 == 0 && Sx % 4 == 0 && Wo % 4 == 0 && ((uintptr_t)tiles & 15) == 0 &&
-                   ((uintptr_t)mean & 15) == 0 && ((uintptr_t)spread & 15) == 0 && (!mask_src || scale % 4 == 0);
-#define SRMI_BLEND_ENS(V, MASK)                                                                                    \
-  hipLaunchKernelGGL((tiles_blend_ensemble_kernel<V, MASK>), dim3((Wo / V + 15) / 16, (Ho + 15) / 16, C), dim3(256), \
-                     0, st, tiles, variants, K, off, dv, bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, mask_src, scale,    \
-                     mean, spread)
-  if (mask_src) {
-    if (vec) SRMI_BLEND_ENS(4, true);
-    else SRMI_BLEND_ENS(1, true);
-  } else {
-    if (vec) SRMI_BLEND_ENS(4, false);
-    else SRMI_BLEND_ENS(1, false);
-  }
-#undef SRMI_BLEND_ENS
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // ------------------------------------------------------ dataset tile statistics
 // _compute_normalization (raw.py:89-106) walks every (tile, variable) plane of every
 // time slice on the host: NormData.add_entry (raw.py:55-60) appends the plane's mean
@@ -1185,25 +1023,6 @@ __global__ void __launch_bounds__(256) tile_stats_kernel(const float* __restrict
   if (threadIdx.x == 0) tile_stats_commit(acc + p * 4, first, m, var, mn, mx);
 }
 
-int tile_stats_launch(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first,
-                      hipStream_t st) {
-  if (n < 1 || C < 1 || ty < 1 || tx < 1 || n * C > 0x7fffffffLL || (long long)ty * tx > 0x7fffffffLL)
-    return SRMI_ERR_SHAPE;
-  if (!tiles || !acc) return SRMI_ERR_ARG;
-  const int ne = ty * tx, n4 = ne / 4;
-  const dim3 grid((unsigned)(n * C));
-  if (ne % 4 || ((uintptr_t)tiles & 15) || n4 > 1024 * kNormKR)
-    hipLaunchKernelGGL(tile_stats_kernel, grid, dim3(256), 0, st, tiles, ne, acc, first);
-  else if (n4 <= 64 * 4)  // up to 32^2: one wave per plane
-    hipLaunchKernelGGL((tile_stats_reg_kernel<64, 4>), grid, dim3(64), 0, st, tiles, n4, acc, first);
-  else if (n4 <= 256 * 4)  // up to 64^2
-    hipLaunchKernelGGL((tile_stats_reg_kernel<256, 4>), grid, dim3(256), 0, st, tiles, n4, acc, first);
-  else  // up to 192^2
-    hipLaunchKernelGGL((tile_stats_reg_kernel<1024, kNormKR>), grid, dim3(1024), 0, st, tiles, n4, acc, first);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // get_norm_stats (raw.py:62-63): row (tile, channel) -> {mean of the means, mean of
 // the variances, max, min}, the reference's STATS order
 __global__ void __launch_bounds__(256) tile_stats_rows_kernel(const double* __restrict__ acc, long long rows,
@@ -1239,19 +1058,6 @@ __global__ void __launch_bounds__(1024) tile_stats_global_kernel(const double* _
   block_minmax<1024>(mn, mx, redf);
   if (threadIdx.x == 0)
     *reinterpret_cast<float4*>(gstats + 4 * c) = make_float4((float)(sm / (double)n), (float)(sv / (double)n), mx, mn);
-}
-
-int tile_stats_finalize_launch(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
-                               hipStream_t st) {
-  if (n < 1 || C < 1 || ntimes < 1 || n * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
-  if (!acc || ((uintptr_t)tstats & 15) || ((uintptr_t)gstats & 15)) return SRMI_ERR_ARG;
-  if (tstats)
-    hipLaunchKernelGGL(tile_stats_rows_kernel, dim3((unsigned)((n * C + 255) / 256)), dim3(256), 0, st, acc, n * C,
-                       (double)ntimes, tstats);
-  if (gstats)
-    hipLaunchKernelGGL(tile_stats_global_kernel, dim3(C), dim3(1024), 0, st, acc, n, C, (double)ntimes, gstats);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // --------------------------------------------------- land-aware overlapped cut
@@ -1464,40 +1270,6 @@ __global__ void __launch_bounds__(kLandThreads) region_to_tiles_masked_kernel(
   }
 }
 
-int region_to_tiles_overlap_masked_launch(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
-                                          int mode, const float* off, const float* dv, float* tiles, float* off_out,
-                                          float* div_out, int* bad, int min_wet, int* nwet, hipStream_t st) {
-  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
-  if (C < 1 || C > 65535 || min_wet < 1) return SRMI_ERR_ARG;  // grid.x
-  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
-  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
-  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
-  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
-      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
-    return SRMI_ERR_ARG;
-  if ((long long)ty * tx > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
-  const bool vec = tx % 4 == 0 && W % 4 == 0 && sx % 4 == 0 && ((uintptr_t)region & 15) == 0 &&
-                   ((uintptr_t)tiles & 15) == 0;
-  const size_t lds = (size_t)ty * tx * (sizeof(float) + sizeof(unsigned short));
-  const dim3 grid(C, gy * gx), block(kLandThreads);
-#define SRMI_R2T_MASKED(MODE, VEC)                                                                                 \
-  hipLaunchKernelGGL((region_to_tiles_masked_kernel<MODE, VEC>), grid, block, lds, st, region, C, H, W, ty, tx, gx, \
-                     sy, sx, min_wet, off, dv, tiles, off_out, div_out, bad, nwet)
-  if (mode == SRMI_NORM_LNORM) {
-    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LNORM, true);
-    else SRMI_R2T_MASKED(SRMI_NORM_LNORM, false);
-  } else if (mode == SRMI_NORM_LSCALE) {
-    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LSCALE, true);
-    else SRMI_R2T_MASKED(SRMI_NORM_LSCALE, false);
-  } else {
-    if (vec) SRMI_R2T_MASKED(SRMI_NORM_AFFINE, true);
-    else SRMI_R2T_MASKED(SRMI_NORM_AFFINE, false);
-  }
-#undef SRMI_R2T_MASKED
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // ------------------------------------------------------- land in training batches
 // No reference counterpart (the reference never trains on a tile with land).
 //
@@ -1538,17 +1310,6 @@ __global__ void __launch_bounds__(kLandThreads) tiles_fill_kernel(float* __restr
     if (passes && tid == 0) passes[p] = np;
     __syncthreads();  // the next plane overwrites the LDS
   }
-}
-
-int tiles_fill_launch(float* tiles, long long nplanes, int h, int w, int* passes, hipStream_t st) {
-  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
-  if ((long long)h * w > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
-  if (!tiles) return SRMI_ERR_ARG;
-  const size_t lds = (size_t)h * w * (sizeof(float) + sizeof(unsigned short));
-  const unsigned grid = (unsigned)(nplanes < 65535 ? nplanes : 65535);
-  hipLaunchKernelGGL(tiles_fill_kernel, dim3(grid), dim3(kLandThreads), lds, st, tiles, nplanes, h, w, passes);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // batch_prep_norm_kernel for tiles with land: the statistics over the wet (finite)
@@ -1681,36 +1442,6 @@ __global__ void __launch_bounds__(kPrepThreads) batch_prep_masked_kernel(
   }
 }
 
-int batch_prep_masked_launch(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
-                             const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
-                             int* nwet, hipStream_t st) {
-  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
-  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
-  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
-  if (lr && (long long)(T / scale) * (T / scale) > kLandMaxPix) return SRMI_ERR_SHAPE;  // tiles_fill's plane
-  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
-  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
-  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
-  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
-  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
-#define SRMI_PREP_MASKED(LDS, MODE, BYTES)                                                                          \
-  hipLaunchKernelGGL((batch_prep_masked_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
-                     lr, off_out, div_out, nwet)
-  if (lds <= 150 * 1024) {
-    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(true, SRMI_NORM_LNORM, lds);
-    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(true, SRMI_NORM_LSCALE, lds);
-    else SRMI_PREP_MASKED(true, SRMI_NORM_AFFINE, lds);
-  } else {
-    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(false, SRMI_NORM_LNORM, 0);
-    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(false, SRMI_NORM_LSCALE, 0);
-    else SRMI_PREP_MASKED(false, SRMI_NORM_AFFINE, 0);
-  }
-#undef SRMI_PREP_MASKED
-  SRMI_CHECK_LAUNCH();
-  if (lr) return tiles_fill_launch(lr, B * C, T / scale, T / scale, nullptr, st);
-  return 0;
-}
-
 // ------------------------------------------------------------ LLC4320 source
 // The reference expands a '>f4' wet-value file through a '>f4' mask template
 // (13 nx^2 cells, 0 = land) on the host, then cuts the east | flipped-west
@@ -1820,36 +1551,6 @@ __global__ void __launch_bounds__(256) llc_map_kernel(const int* __restrict__ ra
   idx[p] = rank[llc_cell(y0 + y, x0 + x, nx)];
 }
 
-int llc_index_map_workspace(long long n, size_t* bytes) {
-  if (n < 1) return SRMI_ERR_SHAPE;
-  const long long nb = (n + kScanBlk - 1) / kScanBlk;
-  *bytes = (size_t)n * 4 + (size_t)nb * 4 + (size_t)nb * 8 + 64;
-  return 0;
-}
-
-int llc_index_map_launch(const uint32_t* tmpl, long long n, int nx, int y0, int ys, int x0, int xs, int* idx,
-                         long long* n_wet, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (nx < 1 || n != 13LL * nx * nx || ys < 1 || xs < 1 || y0 < 0 || x0 < 0 || y0 + ys > 3 * nx ||
-      x0 + xs > 4 * nx)
-    return SRMI_ERR_SHAPE;
-  size_t need = 0;
-  llc_index_map_workspace(n, &need);
-  if (!tmpl || !idx || !n_wet || !ws || ws_bytes < need) return SRMI_ERR_ARG;
-  const long long nb = (n + kScanBlk - 1) / kScanBlk;
-  char* w = static_cast<char*>(ws);
-  int* rank = reinterpret_cast<int*>(w);
-  long long* blkoff = reinterpret_cast<long long*>(w + (((size_t)n * 4 + 7) & ~(size_t)7));
-  int* blkcnt = reinterpret_cast<int*>(reinterpret_cast<char*>(blkoff) + (size_t)nb * 8);
-  hipLaunchKernelGGL(llc_count_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, st, tmpl, n, blkcnt);
-  hipLaunchKernelGGL(llc_scan_counts_kernel, dim3(1), dim3(kScanThreads), 0, st, blkcnt, (int)nb, blkoff, n_wet);
-  hipLaunchKernelGGL(llc_rank_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, st, tmpl, n, blkoff, rank);
-  const long long np = (long long)ys * xs;
-  hipLaunchKernelGGL(llc_map_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, rank, nx, y0, ys, x0, xs,
-                     idx);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // out[p] = float(bswap(data[idx[p]])), NaN for land (idx < 0) or idx >= nvals
 __global__ void __launch_bounds__(256) llc_gather_kernel(const uint32_t* __restrict__ data, long long nvals,
                                                          const int* __restrict__ idx, long long np,
@@ -1858,16 +1559,6 @@ __global__ void __launch_bounds__(256) llc_gather_kernel(const uint32_t* __restr
   if (p >= np) return;
   const int i = idx[p];
   out[p] = (i >= 0 && i < nvals) ? __uint_as_float(__builtin_bswap32(data[i])) : __int_as_float(0x7fc00000);
-}
-
-int llc_gather_launch(const uint32_t* data, long long nvals, const int* idx, long long np, float* out,
-                      hipStream_t st) {
-  if (np < 1 || nvals < 0) return SRMI_ERR_SHAPE;
-  if (!data || !idx || !out) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(llc_gather_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, data, nvals, idx, np,
-                     out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // get_tiles' keep mask: bad[c * gy*gx + t] = 1 when tile t of channel c holds a
@@ -1881,15 +1572,6 @@ __global__ void __launch_bounds__(256) tiles_nonfinite_kernel(const float* __res
   for (int i = threadIdx.x; i < ty * tx; i += 256) nf |= !isfinite(src[(size_t)(i / tx) * W + (i % tx)]);
   nf = __syncthreads_or(nf);
   if (threadIdx.x == 0) bad[(size_t)c * gridDim.x + t] = nf;
-}
-
-int tiles_nonfinite_launch(const float* region, int C, int H, int W, int ty, int tx, int* bad, hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
-  if (!region || !bad) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(tiles_nonfinite_kernel, dim3((H / ty) * (W / tx), C), dim3(256), 0, st, region, H, W, ty, tx,
-                     W / tx, bad);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // tiles_nonfinite_kernel with a threshold, for training on coastal tiles (no reference
@@ -1922,16 +1604,6 @@ __global__ void __launch_bounds__(256) tiles_dry_kernel(const float* __restrict_
   for (int c = threadIdx.x; c < C; c += 256) bad[(size_t)c * ncells + t] = isbad;
 }
 
-int tiles_dry_launch(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
-                     hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
-  if (!region || !bad || min_wet < 1) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(tiles_dry_kernel, dim3((H / ty) * (W / tx)), dim3(256), 0, st, region, C, H, W, ty, tx, W / tx,
-                     min_wet, bad, nwet);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // out plane m (= [m / C][m % C] of the [n/C][C][ty][tx] result) <- tile plane
 // src[m] = c * gy*gx + t of the channel-major flattening.  grid (ceil(ty*tx/1024), nslots)
 __global__ void __launch_bounds__(256) tiles_gather_kernel(const float* __restrict__ region, int H, int W, int ty,
@@ -1944,18 +1616,6 @@ __global__ void __launch_bounds__(256) tiles_gather_kernel(const float* __restri
   float* d = out + (size_t)m * ty * tx;
   for (int i = blockIdx.x * 1024 + threadIdx.x; i < min(ty * tx, (int)(blockIdx.x + 1) * 1024); i += 256)
     d[i] = s[(size_t)(i / tx) * W + (i % tx)];
-}
-
-int tiles_gather_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
-                        float* out, hipStream_t st) {
-  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx || nslots < 0) return SRMI_ERR_SHAPE;
-  if (nslots == 0) return 0;
-  if (!region || !src || !out) return SRMI_ERR_ARG;
-  const int gx = W / tx, ntile = (H / ty) * gx;
-  hipLaunchKernelGGL(tiles_gather_kernel, dim3((ty * tx + 1023) / 1024, nslots), dim3(256), 0, st, region, H, W, ty,
-                     tx, gx, ntile, src, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // ------------------------------------------------- sparse file reads (srmi.feed)
@@ -1977,27 +1637,6 @@ __global__ void __launch_bounds__(256) llc_block_mask_kernel(const int* __restri
   else err[0] = 1;
 }
 
-int llc_block_mask_launch(const int* idx, long long np, int shift, int* mask, int n_blocks, hipStream_t st) {
-  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
-  if (!idx || !mask) return SRMI_ERR_ARG;
-  int* err = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int));
-  if (e != hipSuccess) return -(int)e;
-  int herr = 0;
-  e = hipMemsetAsync(err, 0, sizeof(int), st);
-  if (e == hipSuccess) e = hipMemsetAsync(mask, 0, sizeof(int) * (size_t)n_blocks, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(llc_block_mask_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
-                       mask, n_blocks, err);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(err);
-  if (e != hipSuccess) return -(int)e;
-  return herr ? SRMI_ERR_SHAPE : 0;
-}
-
 // out[p] = block_base[idx >> shift] + (idx & (2^shift - 1)); -1 for land, for a
 // block that is not read (base -1) and for an index past the blocks
 __global__ void __launch_bounds__(256) llc_compact_map_kernel(const int* __restrict__ idx, long long np, int shift,
@@ -2012,16 +1651,6 @@ __global__ void __launch_bounds__(256) llc_compact_map_kernel(const int* __restr
     if (b >= 0) o = b + (i & ((1 << shift) - 1));
   }
   out[p] = o;
-}
-
-int llc_compact_map_launch(const int* idx, long long np, int shift, const int* base, int n_blocks, int* out,
-                           hipStream_t st) {
-  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
-  if (!idx || !base || !out) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(llc_compact_map_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
-                     base, n_blocks, out);
-  SRMI_CHECK_LAUNCH();
-  return 0;
 }
 
 // get_tiles' keep list on the device: keep = flatnonzero(bad == 0), n = len(keep) / C,
@@ -2071,14 +1700,6 @@ __global__ void __launch_bounds__(kKeepThreads) tiles_keep_kernel(const int* __r
   }
 }
 
-int tiles_keep_launch(const int* bad, int C, int ncells, int* src, int* count, hipStream_t st) {
-  if (C < 1 || ncells < 1 || (long long)C * ncells > 0x7fffffffLL) return SRMI_ERR_SHAPE;
-  if (!bad || !src || !count) return SRMI_ERR_ARG;
-  hipLaunchKernelGGL(tiles_keep_kernel, dim3(1), dim3(kKeepThreads), 0, st, bad, C, C * ncells, src, count);
-  SRMI_CHECK_LAUNCH();
-  return 0;
-}
-
 // tiles_gather_kernel with the slot count on the device (count[0] * C, tiles_keep's
 // result): launched for max_slots planes, a plane at or past the count returns
 // before it reads src or writes out.  grid (max_slots, ceil(ty*tx/1024))
@@ -2098,17 +1719,429 @@ __global__ void __launch_bounds__(256) tiles_gather_dev_kernel(const float* __re
     d[i] = s[(size_t)(i / tx) * W + (i % tx)];
 }
 
-int tiles_gather_dev_launch(const float* region, int C, int H, int W, int ty, int tx, const int* src,
-                            const int* count, int max_slots, float* out, hipStream_t st) {
+}  // namespace srmi
+
+using namespace srmi;
+
+extern "C" {
+
+int srmi_region_to_tiles(const float* region, int C, int H, int W, int ty, int tx, float* tiles, float* mean,
+                         float* stdv, int* bad, void* stream) {
+  if (!region || !tiles || !mean || !stdv) return SRMI_ERR_ARG;
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  return region_to_tiles_plan_launch(region, C, H, W, ty, tx, H / ty, W / tx, ty, tx, tiles, mean, stdv, bad,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int srmi_tiles_to_region(const float* tiles, const float* mean, const float* stdv, const int* inv, int C, int ty,
+                         int tx, int gy, int gx, float* out, void* stream) {
+  if (!tiles || !out || (mean && !stdv)) return SRMI_ERR_ARG;
+  if (C < 1 || ty < 1 || tx < 1 || gy < 1 || gx < 1) return SRMI_ERR_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (tx % 4 == 0 && ((uintptr_t)tiles & 15) == 0 && ((uintptr_t)out & 15) == 0) {
+    hipLaunchKernelGGL(tiles_to_region_v4_kernel, dim3((gx * tx / 4 + 255) / 256, gy * ty, C), dim3(256), 0, st,
+                       tiles, mean, stdv, inv, C, ty, tx, gx, out);
+    SRMI_CHECK_LAUNCH();
+    return 0;
+  }
+  hipLaunchKernelGGL(tiles_to_region_kernel, dim3((gx * tx + 255) / 256, gy * ty, C), dim3(256), 0, st, tiles, mean,
+                     stdv, inv, C, ty, tx, gx, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_batch_prep(const float* raw, int B, int C, int T, int flip, int scale, float* hr, float* lr, float* mean,
+                    float* stdv, void* stream) {
+  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7) return SRMI_ERR_SHAPE;
+  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
+  if (!raw || !hr) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (lds <= 150 * 1024) {
+    hipLaunchKernelGGL(batch_prep_kernel<true>, dim3(C, B), dim3(kPrepThreads), lds, st, raw, C, T, flip, scale, hr,
+                       lr, mean, stdv);
+  } else {
+    hipLaunchKernelGGL(batch_prep_kernel<false>, dim3(C, B), dim3(kPrepThreads), 0, st, raw, C, T, flip, scale, hr,
+                       lr, mean, stdv);
+  }
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_batch_prep_norm(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                         const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                         void* stream) {
+  if (mode == SRMI_NORM_LNORM) {
+    if (B > 65535) return SRMI_ERR_SHAPE;  // srmi_batch_prep's grid.y
+    return srmi_batch_prep(raw, (int)B, C, T, flip, scale, hr, lr, off_out, div_out, stream);
+  }
+  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
+  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
+  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
+  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define SRMI_PREP_NORM(LDS, MODE, BYTES)                                                                          \
+  hipLaunchKernelGGL((batch_prep_norm_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
+                     lr, off_out, div_out)
+  if (lds <= 150 * 1024) {
+    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(true, SRMI_NORM_LSCALE, lds);
+    else SRMI_PREP_NORM(true, SRMI_NORM_AFFINE, lds);
+  } else {
+    if (mode == SRMI_NORM_LSCALE) SRMI_PREP_NORM(false, SRMI_NORM_LSCALE, 0);
+    else SRMI_PREP_NORM(false, SRMI_NORM_AFFINE, 0);
+  }
+#undef SRMI_PREP_NORM
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_region_to_tiles_norm(const float* region, int C, int H, int W, int ty, int tx, int mode, const float* off,
+                              const float* dv, float* tiles, float* off_out, float* div_out, int* bad,
+                              void* stream) {
+  if (mode == SRMI_NORM_LNORM) {
+    if (!region || !tiles || !off_out || !div_out) return SRMI_ERR_ARG;
+    return srmi_region_to_tiles(region, C, H, W, ty, tx, tiles, off_out, div_out, bad, stream);
+  }
+  if (mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  const int gy = H / ty, gx = W / tx;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, ty, tx, mode, off, dv, tiles, off_out,
+                                          div_out, bad, static_cast<hipStream_t>(stream));
+}
+
+int srmi_overlap_count(int L, int t, int S) { return overlap_count(L, t, S); }
+
+int srmi_region_to_tiles_overlap(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx, int mode,
+                                 const float* off, const float* dv, float* tiles, float* off_out, float* div_out,
+                                 int* bad, void* stream) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.x
+  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
+  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
+      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
+    return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (mode == SRMI_NORM_LNORM)
+    return region_to_tiles_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, tiles, off_out, div_out, bad, st);
+  return region_to_tiles_norm_plan_launch(region, C, H, W, ty, tx, gy, gx, sy, sx, mode, off, dv, tiles, off_out,
+                                          div_out, bad, st);
+}
+
+int srmi_tiles_blend(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty, int Tx,
+                     int Sy, int Sx, int Ho, int Wo, float* out, void* stream) {
+  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, nullptr, 1, out,
+                                static_cast<hipStream_t>(stream));
+}
+
+int srmi_tiles_blend_masked(const float* tiles, const float* off, const float* dv, const int* bad, int C, int Ty,
+                            int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src, int scale, float* out,
+                            void* stream) {
+  if (!mask_src || scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale) return SRMI_ERR_ARG;
+  return tiles_blend_any_launch(tiles, off, dv, bad, C, Ty, Tx, Sy, Sx, Ho, Wo, mask_src, scale, out,
+                                static_cast<hipStream_t>(stream));
+}
+
+int srmi_tiles_dihedral(const float* in, long long nplanes, int h, int w, int variants, float* out, void* stream) {
+  if (variants < 1 || variants > 255 || !in || !out || in == out) return SRMI_ERR_ARG;
+  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
+  if ((variants & 0xf0) && h != w) return SRMI_ERR_SHAPE;  // a swap of a rectangular plane
+  const int nby = (h + kDihB - 1) / kDihB, nbx = (w + kDihB - 1) / kDihB;
+  if (nplanes * nby * nbx > 0x7fffffffLL) return SRMI_ERR_SHAPE;  // grid.x
+  const size_t slab = (size_t)nplanes * h * w;
+  const dim3 grid((unsigned)(nplanes * nby * nbx));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (w % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL(tiles_dihedral_kernel<true>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
+  else
+    hipLaunchKernelGGL(tiles_dihedral_kernel<false>, grid, dim3(256), 0, st, in, h, w, nby, nbx, variants, slab, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_blend_ensemble(const float* tiles, int variants, const float* off, const float* dv, const int* bad,
+                              int C, int Ty, int Tx, int Sy, int Sx, int Ho, int Wo, const float* mask_src,
+                              int scale, float* mean, float* spread, void* stream) {
+  if (variants < 1 || variants > 255) return SRMI_ERR_ARG;
+  if (mask_src && (scale < 1 || Ho < 1 || Wo < 1 || Ho % scale || Wo % scale)) return SRMI_ERR_ARG;
+  // from here as tiles_blend_any_launch
+  if (C < 1 || C > 65535) return SRMI_ERR_ARG;  // grid.z
+  const int ny = overlap_count(Ho, Ty, Sy), nx = overlap_count(Wo, Tx, Sx);
+  if (ny < 0 || nx < 0) return SRMI_ERR_ARG;
+  const long long wy = (long long)(Ty / Sy + 2) * (Ty - Sy + 1), wx = (long long)(Tx / Sx + 2) * (Tx - Sx + 1);
+  if (Ho > 65535 || (long long)ny * nx > 0x7fffffffLL || wy * wx > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if ((variants & 0xf0) && Ty != Tx) return SRMI_ERR_SHAPE;  // a swap of a rectangular tile
+  if (!tiles || !mean || (off && !dv)) return SRMI_ERR_ARG;
+  const int K = __builtin_popcount((unsigned)variants);
+  const bool vec = Tx % 4 == 0 && Sx % 4 == 0 && Wo % 4 == 0 && ((uintptr_t)tiles & 15) == 0 &&
+                   ((uintptr_t)mean & 15) == 0 && ((uintptr_t)spread & 15) == 0 && (!mask_src || scale % 4 == 0);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define SRMI_BLEND_ENS(V, MASK)                                                                                    \
+  hipLaunchKernelGGL((tiles_blend_ensemble_kernel<V, MASK>), dim3((Wo / V + 15) / 16, (Ho + 15) / 16, C), dim3(256), \
+                     0, st, tiles, variants, K, off, dv, bad, C, Ty, Tx, Sy, Sx, ny, nx, Ho, Wo, mask_src, scale,    \
+                     mean, spread)
+  if (mask_src) {
+    if (vec) SRMI_BLEND_ENS(4, true);
+    else SRMI_BLEND_ENS(1, true);
+  } else {
+    if (vec) SRMI_BLEND_ENS(4, false);
+    else SRMI_BLEND_ENS(1, false);
+  }
+#undef SRMI_BLEND_ENS
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tile_stats(const float* tiles, long long n, int C, int ty, int tx, double* acc, int first, void* stream) {
+  if (n < 1 || C < 1 || ty < 1 || tx < 1 || n * C > 0x7fffffffLL || (long long)ty * tx > 0x7fffffffLL)
+    return SRMI_ERR_SHAPE;
+  if (!tiles || !acc) return SRMI_ERR_ARG;
+  const int ne = ty * tx, n4 = ne / 4;
+  const dim3 grid((unsigned)(n * C));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (ne % 4 || ((uintptr_t)tiles & 15) || n4 > 1024 * kNormKR)
+    hipLaunchKernelGGL(tile_stats_kernel, grid, dim3(256), 0, st, tiles, ne, acc, first);
+  else if (n4 <= 64 * 4)  // up to 32^2: one wave per plane
+    hipLaunchKernelGGL((tile_stats_reg_kernel<64, 4>), grid, dim3(64), 0, st, tiles, n4, acc, first);
+  else if (n4 <= 256 * 4)  // up to 64^2
+    hipLaunchKernelGGL((tile_stats_reg_kernel<256, 4>), grid, dim3(256), 0, st, tiles, n4, acc, first);
+  else  // up to 192^2
+    hipLaunchKernelGGL((tile_stats_reg_kernel<1024, kNormKR>), grid, dim3(1024), 0, st, tiles, n4, acc, first);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tile_stats_finalize(const double* acc, long long n, int C, int ntimes, float* tstats, float* gstats,
+                             void* stream) {
+  if (n < 1 || C < 1 || ntimes < 1 || n * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (!acc || ((uintptr_t)tstats & 15) || ((uintptr_t)gstats & 15)) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (tstats)
+    hipLaunchKernelGGL(tile_stats_rows_kernel, dim3((unsigned)((n * C + 255) / 256)), dim3(256), 0, st, acc, n * C,
+                       (double)ntimes, tstats);
+  if (gstats)
+    hipLaunchKernelGGL(tile_stats_global_kernel, dim3(C), dim3(1024), 0, st, acc, n, C, (double)ntimes, gstats);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_region_to_tiles_overlap_masked(const float* region, int C, int H, int W, int ty, int tx, int sy, int sx,
+                                        int mode, const float* off, const float* dv, float* tiles, float* off_out,
+                                        float* div_out, int* bad, int min_wet, int* nwet, void* stream) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (C < 1 || C > 65535 || min_wet < 1) return SRMI_ERR_ARG;  // grid.x
+  const int gy = overlap_count(H, ty, sy), gx = overlap_count(W, tx, sx);
+  if (gy < 0 || gx < 0) return SRMI_ERR_ARG;
+  if ((long long)gy * gx > 65535) return SRMI_ERR_SHAPE;  // grid.y, as region_to_tiles
+  if (!region || !tiles || (mode == SRMI_NORM_AFFINE && (!off || !dv)) ||
+      (mode == SRMI_NORM_LNORM && (!off_out || !div_out)))
+    return SRMI_ERR_ARG;
+  if ((long long)ty * tx > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
+  const bool vec = tx % 4 == 0 && W % 4 == 0 && sx % 4 == 0 && ((uintptr_t)region & 15) == 0 &&
+                   ((uintptr_t)tiles & 15) == 0;
+  const size_t lds = (size_t)ty * tx * (sizeof(float) + sizeof(unsigned short));
+  const dim3 grid(C, gy * gx), block(kLandThreads);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define SRMI_R2T_MASKED(MODE, VEC)                                                                                 \
+  hipLaunchKernelGGL((region_to_tiles_masked_kernel<MODE, VEC>), grid, block, lds, st, region, C, H, W, ty, tx, gx, \
+                     sy, sx, min_wet, off, dv, tiles, off_out, div_out, bad, nwet)
+  if (mode == SRMI_NORM_LNORM) {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LNORM, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_LNORM, false);
+  } else if (mode == SRMI_NORM_LSCALE) {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_LSCALE, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_LSCALE, false);
+  } else {
+    if (vec) SRMI_R2T_MASKED(SRMI_NORM_AFFINE, true);
+    else SRMI_R2T_MASKED(SRMI_NORM_AFFINE, false);
+  }
+#undef SRMI_R2T_MASKED
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_fill(float* tiles, long long nplanes, int h, int w, int* passes, void* stream) {
+  if (nplanes < 1 || h < 1 || w < 1) return SRMI_ERR_SHAPE;
+  if ((long long)h * w > kLandMaxPix) return SRMI_ERR_SHAPE;  // values + stamps in LDS
+  if (!tiles) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)h * w * (sizeof(float) + sizeof(unsigned short));
+  const unsigned grid = (unsigned)(nplanes < 65535 ? nplanes : 65535);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tiles_fill_kernel, dim3(grid), dim3(kLandThreads), lds, st, tiles, nplanes, h, w, passes);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_batch_prep_masked(const float* raw, long long B, int C, int T, int flip, int scale, int mode,
+                           const float* off, const float* dv, float* hr, float* lr, float* off_out, float* div_out,
+                           int* nwet, void* stream) {
+  if (mode != SRMI_NORM_LNORM && mode != SRMI_NORM_LSCALE && mode != SRMI_NORM_AFFINE) return SRMI_ERR_ARG;
+  if (B < 1 || C < 1 || T < 2 || T % 2 || flip < 0 || flip > 7 || B * C > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (lr && (scale < 2 || T % scale)) return SRMI_ERR_SHAPE;
+  if (lr && (long long)(T / scale) * (T / scale) > kLandMaxPix) return SRMI_ERR_SHAPE;  // tiles_fill's plane
+  if (!raw || !hr || (mode == SRMI_NORM_AFFINE && (!off || !dv))) return SRMI_ERR_ARG;
+  // the kernel's float4 loads and stores: T even makes every plane a multiple of 16 bytes
+  if (((uintptr_t)raw | (uintptr_t)hr) & 15) return SRMI_ERR_ARG;
+  const size_t lds = (size_t)T * (T + 1) * sizeof(float);
+  const dim3 grid((unsigned)(B * C)), block(kPrepThreads);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define SRMI_PREP_MASKED(LDS, MODE, BYTES)                                                                          \
+  hipLaunchKernelGGL((batch_prep_masked_kernel<LDS, MODE>), grid, block, BYTES, st, raw, T, flip, scale, off, dv, hr, \
+                     lr, off_out, div_out, nwet)
+  if (lds <= 150 * 1024) {
+    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(true, SRMI_NORM_LNORM, lds);
+    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(true, SRMI_NORM_LSCALE, lds);
+    else SRMI_PREP_MASKED(true, SRMI_NORM_AFFINE, lds);
+  } else {
+    if (mode == SRMI_NORM_LNORM) SRMI_PREP_MASKED(false, SRMI_NORM_LNORM, 0);
+    else if (mode == SRMI_NORM_LSCALE) SRMI_PREP_MASKED(false, SRMI_NORM_LSCALE, 0);
+    else SRMI_PREP_MASKED(false, SRMI_NORM_AFFINE, 0);
+  }
+#undef SRMI_PREP_MASKED
+  SRMI_CHECK_LAUNCH();
+  if (lr) return srmi_tiles_fill(lr, B * C, T / scale, T / scale, nullptr, stream);
+  return 0;
+}
+
+int srmi_llc_index_map_workspace(long long n, size_t* bytes) {
+  if (!bytes) return SRMI_ERR_ARG;
+  if (n < 1) return SRMI_ERR_SHAPE;
+  const long long nb = (n + kScanBlk - 1) / kScanBlk;
+  *bytes = (size_t)n * 4 + (size_t)nb * 4 + (size_t)nb * 8 + 64;
+  return 0;
+}
+
+int srmi_llc_index_map(const void* template_be, long long n, int nx, int y0, int ys, int x0, int xs, int* idx,
+                       long long* n_wet, void* ws, size_t ws_bytes, void* stream) {
+  const uint32_t* tmpl = static_cast<const uint32_t*>(template_be);
+  if (nx < 1 || n != 13LL * nx * nx || ys < 1 || xs < 1 || y0 < 0 || x0 < 0 || y0 + ys > 3 * nx ||
+      x0 + xs > 4 * nx)
+    return SRMI_ERR_SHAPE;
+  size_t need = 0;
+  srmi_llc_index_map_workspace(n, &need);
+  if (!tmpl || !idx || !n_wet || !ws || ws_bytes < need) return SRMI_ERR_ARG;
+  const long long nb = (n + kScanBlk - 1) / kScanBlk;
+  char* w = static_cast<char*>(ws);
+  int* rank = reinterpret_cast<int*>(w);
+  long long* blkoff = reinterpret_cast<long long*>(w + (((size_t)n * 4 + 7) & ~(size_t)7));
+  int* blkcnt = reinterpret_cast<int*>(reinterpret_cast<char*>(blkoff) + (size_t)nb * 8);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(llc_count_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, st, tmpl, n, blkcnt);
+  hipLaunchKernelGGL(llc_scan_counts_kernel, dim3(1), dim3(kScanThreads), 0, st, blkcnt, (int)nb, blkoff, n_wet);
+  hipLaunchKernelGGL(llc_rank_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, st, tmpl, n, blkoff, rank);
+  const long long np = (long long)ys * xs;
+  hipLaunchKernelGGL(llc_map_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, rank, nx, y0, ys, x0, xs,
+                     idx);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_llc_gather(const void* data_be, long long nvals, const int* idx, long long np, float* out, void* stream) {
+  const uint32_t* data = static_cast<const uint32_t*>(data_be);
+  if (np < 1 || nvals < 0) return SRMI_ERR_SHAPE;
+  if (!data || !idx || !out) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(llc_gather_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, data, nvals, idx, np,
+                     out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_nonfinite(const float* region, int C, int H, int W, int ty, int tx, int* bad, void* stream) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  if (!region || !bad) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tiles_nonfinite_kernel, dim3((H / ty) * (W / tx), C), dim3(256), 0, st, region, H, W, ty, tx,
+                     W / tx, bad);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_dry(const float* region, int C, int H, int W, int ty, int tx, int min_wet, int* bad, int* nwet,
+                   void* stream) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx) return SRMI_ERR_SHAPE;
+  if (!region || !bad || min_wet < 1) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tiles_dry_kernel, dim3((H / ty) * (W / tx)), dim3(256), 0, st, region, C, H, W, ty, tx, W / tx,
+                     min_wet, bad, nwet);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_gather(const float* region, int C, int H, int W, int ty, int tx, const int* src, int nslots,
+                      float* out, void* stream) {
+  if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx || nslots < 0) return SRMI_ERR_SHAPE;
+  if (nslots == 0) return 0;
+  if (!region || !src || !out) return SRMI_ERR_ARG;
+  const int gx = W / tx, ntile = (H / ty) * gx;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tiles_gather_kernel, dim3((ty * tx + 1023) / 1024, nslots), dim3(256), 0, st, region, H, W, ty,
+                     tx, gx, ntile, src, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_llc_block_mask(const int* idx, long long np, int shift, int* mask, int n_blocks, void* stream) {
+  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
+  if (!idx || !mask) return SRMI_ERR_ARG;
+  int* err = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int));
+  if (e != hipSuccess) return -(int)e;
+  int herr = 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  e = hipMemsetAsync(err, 0, sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(mask, 0, sizeof(int) * (size_t)n_blocks, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(llc_block_mask_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
+                       mask, n_blocks, err);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(err);
+  if (e != hipSuccess) return -(int)e;
+  return herr ? SRMI_ERR_SHAPE : 0;
+}
+
+int srmi_llc_compact_map(const int* idx, long long np, int shift, const int* base, int n_blocks, int* out,
+                         void* stream) {
+  if (np < 1 || shift < 0 || shift > 30 || n_blocks < 1) return SRMI_ERR_SHAPE;
+  if (!idx || !base || !out) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(llc_compact_map_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, idx, np, shift,
+                     base, n_blocks, out);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_keep(const int* bad, int C, int ncells, int* src, int* count, void* stream) {
+  if (C < 1 || ncells < 1 || (long long)C * ncells > 0x7fffffffLL) return SRMI_ERR_SHAPE;
+  if (!bad || !src || !count) return SRMI_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tiles_keep_kernel, dim3(1), dim3(kKeepThreads), 0, st, bad, C, C * ncells, src, count);
+  SRMI_CHECK_LAUNCH();
+  return 0;
+}
+
+int srmi_tiles_gather_dev(const float* region, int C, int H, int W, int ty, int tx, const int* src,
+                          const int* count, int max_slots, float* out, void* stream) {
   if (C < 1 || ty < 1 || tx < 1 || H < ty || W < tx || max_slots < 0) return SRMI_ERR_SHAPE;
   if ((long long)ty * tx > 65535LL * 1024) return SRMI_ERR_SHAPE;  // grid.y
   if (max_slots == 0) return 0;
   if (!region || !src || !count || !out) return SRMI_ERR_ARG;
   const int gx = W / tx, ntile = (H / ty) * gx;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(tiles_gather_dev_kernel, dim3(max_slots, (ty * tx + 1023) / 1024), dim3(256), 0, st, region, C, H,
                      W, ty, tx, gx, ntile, src, count, out);
   SRMI_CHECK_LAUNCH();
   return 0;
 }
 
-}  // namespace srmi
+}  // extern "C"

@@ -31,8 +31,7 @@
 namespace srmi {
 
 static __device__ uint4 kZerosW[4];  // zero page for halo lanes of the stage DMA
-static unsigned long long* g_wg_stamps = nullptr;
-void wgrad3x3_set_debug_stamps(unsigned long long* buf) { g_wg_stamps = buf; }
+static unsigned long long* g_wg_stamps = nullptr;  // (srmi_debug_wgrad_stamps, below, sets it)
 #ifdef SRMI_STAMPS
 #define WSTAMP(i)                                                                                     \
   do {                                                                                                \
@@ -958,3 +957,14 @@ int wgrad_reduce_sets_launch(const ReduceSet* sets, int n, hipStream_t st) {
 }
 
 }  // namespace srmi
+
+using namespace srmi;
+
+extern "C" {
+
+int srmi_debug_wgrad_stamps(void* buf) {
+  g_wg_stamps = (unsigned long long*)buf;
+  return 0;
+}
+
+}  // extern "C"

@@ -68,8 +68,8 @@ import torch
 
 U = 2.0 ** -24
 CLASSES = ("m", "v", "p", "moved")
-GRID_SPAN = 8192 * 256      # adam_launch's grid cap in elements: the loop's second trip starts here
-AXPY_SPAN = 4096 * 256      # scale_add_launch's
+GRID_SPAN = 8192 * 256      # srmi_adam_step's grid cap in elements: the loop's second trip starts here
+AXPY_SPAN = 4096 * 256      # srmi_axpy's
 MOVED_MIN = 0.99
 
 

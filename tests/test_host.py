@@ -503,6 +503,60 @@ def test_conv_abi_rejects_missing_operands():
         assert lib.srmi_pack_conv(dummy, dummy, 64, 256, 1, dummy, dummy, dummy, dtype, None) == -10002
 
 
+def test_stateless_abi_return_codes():
+    """The stateless entry points (defined beside their kernels) refuse bad arguments with
+    the documented code, and where two checks reject the same call, with the first one's.
+    Every case fails validation before any HIP call, so this needs no GPU."""
+    import ctypes as C
+    from srmi import _lib
+    lib = _lib.load()
+    ARG, SHAPE = -10001, -10002
+    d = C.c_void_p(16)  # never dereferenced: every case below fails validation first
+    nbytes = C.c_size_t()
+    nan = float("nan")
+    cases = [
+        # small.hip: the loss sums
+        ("tile_loss_parts pred NULL", lib.srmi_tile_loss_parts, (None, d, 1, 64, 0, 0.0, d, None), ARG),
+        ("tile_loss_parts kind 2", lib.srmi_tile_loss_parts, (d, d, 1, 64, 2, 0.0, d, None), ARG),
+        ("loss_from_parts kind -2", lib.srmi_loss_from_parts, (d, 1, 64.0, -2, d, None), ARG),
+        ("loss_combine nparts 0", lib.srmi_loss_combine, (d, d, 0, 0, None), ARG),
+        # small.hip: the optimizer
+        ("adam_step step 0", lib.srmi_adam_step, (d, d, d, d, 4, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, None), ARG),
+        ("adam_step_guarded ctl NULL", lib.srmi_adam_step_guarded,
+         (d, d, d, d, None, 4, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.0, None, None), ARG),
+        ("adam_step_guarded ema_decay 1", lib.srmi_adam_step_guarded,
+         (d, d, d, d, d, 4, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, d, None), ARG),
+        ("grad_norm_workspace n 0", lib.srmi_grad_norm_workspace, (0, C.byref(nbytes)), ARG),
+        ("grad_norm_workspace bytes NULL", lib.srmi_grad_norm_workspace, (4, None), ARG),
+        ("grad_norm max_norm 0", lib.srmi_grad_norm, (d, 4, 0.0, d, 1 << 20, d, None), ARG),
+        ("grad_norm max_norm NaN", lib.srmi_grad_norm, (d, 4, nan, d, 1 << 20, d, None), ARG),
+        ("grad_norm workspace misaligned", lib.srmi_grad_norm, (d, 4, 1.0, C.c_void_p(20), 1 << 20, d, None), ARG),
+        # small.hip and tiles.hip: pointer and dtype checks that stood in the forwarders
+        ("region_to_tiles mean NULL", lib.srmi_region_to_tiles, (d, 1, 48, 48, 48, 48, d, None, d, None, None), ARG),
+        ("tiles_to_region std NULL", lib.srmi_tiles_to_region, (d, d, None, None, 1, 48, 48, 1, 1, d, None), ARG),
+        ("axpy x NULL", lib.srmi_axpy, (d, None, 1.0, 4, None), ARG),
+        ("llc_index_map_workspace bytes NULL", lib.srmi_llc_index_map_workspace, (13, None), ARG),
+        ("pack_conv dtype 7", lib.srmi_pack_conv, (d, d, 64, 64, 0, d, d, d, 7, None), ARG),
+        # the order of checks: the shape before the pointers
+        ("tiles_nonfinite C 0, region NULL", lib.srmi_tiles_nonfinite, (None, 0, 48, 48, 48, 48, d, None), SHAPE),
+        ("tiles_nonfinite region NULL", lib.srmi_tiles_nonfinite, (None, 1, 48, 48, 48, 48, d, None), ARG),
+        ("upsample scale 0", lib.srmi_upsample, (d, 1, 1, 48, 48, 0, d, None), SHAPE),
+        # tiles.hip: the tile count of an overlapped axis
+        ("overlap_count stride 0", lib.srmi_overlap_count, (10, 4, 0), ARG),
+        ("overlap_count one tile", lib.srmi_overlap_count, (48, 48, 48), 1),
+        ("overlap_count shifted last tile", lib.srmi_overlap_count, (100, 48, 26), 3),
+        # the score and loss files
+        ("ssim_workspace H 10", lib.srmi_ssim_workspace, (1, 10, 48, C.byref(nbytes)), ARG),
+        ("ssim_workspace bytes NULL", lib.srmi_ssim_workspace, (1, 48, 48, None), ARG),
+        ("ssim_loss_from_parts nplanes 0", lib.srmi_ssim_loss_from_parts, (d, d, 0, 1.0, d, d, d, None), ARG),
+        ("spectra_workspace bytes NULL", lib.srmi_spectra_workspace, (1, 64, 64, 32, 16, None), ARG),
+        ("spectral_loss_from_parts P 8", lib.srmi_spectral_loss_from_parts, (d, d, 1, 8, 1.0, d, d, d, None), ARG),
+        ("quantile_map_fit nbins 1", lib.srmi_quantile_map_fit, (d, d, 1, 1, None, 0, d, d, d, None), ARG),
+    ]
+    for name, fn, args, want in cases:
+        assert fn(*args) == want, name
+
+
 def _force_dp_rank(port, q):
     import os as _os
     import sys as _sys
