@@ -6,10 +6,15 @@ SRC := $(PKG)/csrc
 OUT := $(PKG)/srmi/libsrmi.so
 OBJDIR ?= build/obj
 CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function -Iinclude $(EXTRA)
-HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip
+HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip $(SRC)/gradient.hip $(SRC)/gradient_loss.hip
 CPPSRC := $(SRC)/engine.cpp
 OBJS := $(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIPSRC)) $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(CPPSRC))
 HDRS := $(wildcard $(SRC)/*.hpp) include/srmi.h
+
+# the gradient score and loss term state their arithmetic operation by operation (srmi.h): their
+# roots and quotients must be the correctly rounded ones, whatever the compiler's default is
+GRADOBJS := $(OBJDIR)/gradient.o $(OBJDIR)/gradient_loss.o build/obj_stamps/gradient.o build/obj_stamps/gradient_loss.o
+$(GRADOBJS): CXXFLAGS += -fhip-fp32-correctly-rounded-divide-sqrt
 
 all: $(OUT)
 

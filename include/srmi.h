@@ -103,6 +103,17 @@
  *   srmi_consistency_adjoint_apply -> the transpose of that correction, for training
  *                                   through it as the model's last layer.  No reference
  *                                   counterpart: the reference's networks are free regressors.
+ *   srmi_gradient_workspace,
+ *   srmi_gradient                -> Sobel gradients of a prediction and of a truth: mean
+ *                                   magnitudes, sharpness, magnitude and vector RMSE, cosine,
+ *                                   and the two magnitude maps.  No reference counterpart:
+ *                                   the reference scores a field by its RMSE alone.
+ *   srmi_gradient_loss_workspace,
+ *   srmi_gradient_loss_parts,
+ *   srmi_gradient_loss_from_parts,
+ *   srmi_gradient_loss_dy        -> a term on the Sobel gradient of the error beside the pixel
+ *                                   loss of a training step.  No reference counterpart: the
+ *                                   reference trains on a pixel loss alone.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -789,6 +800,45 @@ int srmi_distribution(const float* a, const float* b, int C, int H, int W, int n
                       const double* probs, int nprobs, void* workspace, size_t workspace_bytes, long long* hist,
                       long long* joint, float* range, long long* count, double* derived, int flags, void* stream);
 
+/* ---- the gradient score (no reference counterpart) ----------------------- */
+/* Are the prediction's fronts as sharp as the truth's, in the right place and pointing the
+ * right way?  pred and truth [C][H][W] fp32 on the device, possibly with NaN / Inf, per
+ * channel; tests/gradient_oracle.py restates it in numpy.
+ *   Operator: the Sobel derivative at unit scale on a plane f[H][W], differences before sums
+ *   (a field at 290 +- 1.5 loses nothing in fp32):
+ *     dX(y, x) = f(y, x+1) - f(y, x-1)            dY(y, x) = f(y+1, x) - f(y-1, x)
+ *     Gx(y, x) = ((dX(y-1, x) + dX(y+1, x)) + 2 dX(y, x)) / 8
+ *     Gy(y, x) = ((dY(y, x-1) + dY(y, x+1)) + 2 dY(y, x)) / 8
+ *   at the VALID positions only, 1 <= y <= H - 2 and 1 <= x <= W - 2: Hv Wv = (H - 2)(W - 2).
+ *   A position is USED iff the nine pixels of its window are finite in pred and in truth of
+ *   that plane: NaN and Inf are the mask, a coast costs a one-pixel rim, windows never cross
+ *   planes.  There is one operator and no option for another.
+ *   gx = Gx inv_dx, gy = Gy inv_dy (inv_dy, inv_dx: the reciprocals of the grid spacing, fp32,
+ *   finite and > 0), |g|^2 = gx gx + gy gy and |g| = sqrt(|g|^2), every operation rounded once
+ *   in fp32, none contracted.
+ * Per channel over the used positions, in fp64 from those fp32 values, in a fixed order
+ * (positions within a workgroup's 16 x 64 rectangle by a fixed tree, rectangles in 256
+ * contiguous shares and a fixed tree), without atomics: count [C] int64 = n and
+ *   sums [C][7] = {sum |g_p|, sum |g_t|, sum (|g_p| - |g_t|)^2, sum |g_p - g_t|^2 (the vector
+ *   difference), sum g_p . g_t, sum |g_p|^2, sum |g_t|^2};
+ *   stats [C][6] = {mean_pred = sums[0] / n, mean_truth = sums[1] / n, sharpness = mean_pred /
+ *   mean_truth (below 1: too smooth), rmse_mag = sqrt(sums[2] / n), rmse_vec = sqrt(sums[3] /
+ *   n), cosine = sums[4] / sqrt(sums[5] sums[6])}, formed on the device.
+ *   n == 0: count 0 and NaN in every entry of sums and stats.
+ * gmag_pred, gmag_truth [C][H][W] fp32, each optional (NULL): |g_p| and |g_t| at the used
+ * positions, NaN at every other pixel, the one-pixel border included.
+ * srmi_gradient_workspace (host only) gives the bytes of `workspace` (16-byte aligned; it need
+ * not be initialised).  Two launches on `stream`, no global atomics, no host synchronisation,
+ * no allocation: capturable, and bit-identical from run to run.  Rows are loaded and the maps
+ * stored 16 bytes at a time when W % 4 == 0 and every buffer is 16-byte aligned, one float at
+ * a time otherwise: the same bits.  H or W < 3, H W >= 2^31, C < 1, a factor that is not
+ * finite or not positive, a missing pred, truth, workspace, count, sums or stats, a workspace
+ * that is too small or misaligned: SRMI_ERR_ARG, nothing launched and no output touched. */
+int srmi_gradient_workspace(int C, int H, int W, size_t* bytes);
+int srmi_gradient(const float* pred, const float* truth, int C, int H, int W, float inv_dy, float inv_dx,
+                  void* workspace, size_t workspace_bytes, long long* count, double* sums, double* stats,
+                  float* gmag_pred, float* gmag_truth, void* stream);
+
 /* ---- quantile mapping (no reference counterpart) ------------------------- */
 /* Empirical quantile mapping: a monotone transfer function T = F_truth^-1 o F_src, calibrated
  * on fields whose truth is known and applied to later ones, so that the mapped output has the
@@ -1036,6 +1086,59 @@ int srmi_ssim_loss_from_parts(const float* parts, const float* cparts, long long
                               const float* base, float* ssim4, float* total, void* stream);
 int srmi_ssim_loss_dy(const void* workspace, size_t workspace_bytes, const float* pred, const float* target,
                       long long nplanes, int H, int W, float weight, const float* ssim4, float* dy, void* stream);
+
+/* ---- the gradient loss term (no reference counterpart) ------------------ */
+/* A first-derivative term beside the pixel loss of a training step: the mean Charbonnier
+ * magnitude of the Sobel gradient of the error.  pred and target [nplanes][H][W] fp32 on the
+ * device (nplanes = N C), possibly with NaN / Inf; tests/gradient_oracle.py restates it in
+ * fp64.  The operator, the valid positions and the rule for a USED position are those of "the
+ * gradient score" above, at unit spacing (training tiles are normalised).
+ *   e = pred - target in fp32, 0 where the pixel is not finite in both.  At a used position:
+ *   a = Gx[e], b = Gy[e], phi = sqrt(a a + b b + eps), eps under the root as in the reference's
+ *   Charbonnier (dual_trainer.py:122, :197), every operation rounded once in fp32 in that
+ *   order, none contracted.
+ *   S = the sum of phi over the used positions of all planes of the (global) batch, Nused
+ *   their number, L_grad = S / Nused; Nused = 0: L_grad = 0 and its gradient is 0, not NaN.
+ *   Gradient: U = a / phi, V = b / phi at the used positions, 0 at every other.  dS / dpred (q)
+ *   = (Gx^T U)(q) + (Gy^T V)(q), the transposes the zero-extended ("full") correlations of the
+ *   [Hv][Wv] maps back onto [H][W]; since the operator is antisymmetric this is -(Gx[U] +
+ *   Gy[V])(q) with the operator applied to the zero-extended maps, which is how it is formed:
+ *   the same operation order, then one addition, then the sign.
+ * Every sum over positions, tiles and planes is in fp64 or integers in a fixed order, no
+ * atomics: bit-identical from run to run, whatever the workspace held, and the same bits
+ * whether the planes go through one call or several.
+ * srmi_gradient_loss_workspace (host only): the bytes of `workspace` (16-byte aligned, need
+ * not be initialised) for nplanes planes; it is laid out plane by plane, bytes / nplanes each,
+ * so a call over planes p0 .. p0 + n - 1 of a batch takes the batch's workspace + p0 * (bytes
+ * / nplanes).  It holds the per-workgroup sums and counts of srmi_gradient_loss_parts only.
+ * srmi_gradient_loss_parts: two launches (tile pass, per-plane sum).  parts[nplanes]: per
+ * plane the fp64 sum of phi over its used positions, rounded once to fp32; cparts[nplanes]:
+ * their count as a float (exact: H W <= 2^24).
+ * srmi_gradient_loss_from_parts: parts and cparts [nplanes] summed over the planes of the
+ * (global) batch in fp64 in a fixed grouping -- 256 contiguous shares of ceil(nplanes / 256)
+ * planes, each in plane order, then the shares in order: the plain sum in plane order up to
+ * 256 planes, and for any nplanes independent of how the planes were split over calls; grad4 = {S, Nused, 1 / Nused, L_grad} (all 0 when
+ * Nused = 0) and total[0] = fma(weight, grad4[3], base[0]).  base: one device float, the total
+ * of the terms before this one; it is only read.
+ * srmi_gradient_loss_dy: dy [nplanes][H][W] = fma(weight grad4[2], dS / dpred, dy), the scale
+ * read from the device, one rounding, one writer per pixel.  It RECOMPUTES U and V from pred
+ * and target (a workgroup stages its rectangle of e with a two-pixel halo in LDS) and so takes
+ * no workspace: storing the two maps would move 8 plane-sized transfers over the two launches
+ * instead of 6.  A pixel that is not finite in both pred and target is not written; weight ==
+ * 0 launches nothing.
+ * Rows are loaded and stored 16 bytes at a time when W % 4 == 0 and pred, target (and dy) are
+ * 16-byte aligned, one float at a time otherwise: the same bits.
+ * All three: `stream`, no allocation, no host read, capturable.  SRMI_ERR_ARG, nothing
+ * launched and no output touched: H or W < 3; H W > 2^24; nplanes < 1; eps <= 0 or not finite;
+ * weight < 0 or not finite; a missing buffer; a workspace that is too small or not 16-byte
+ * aligned. */
+int srmi_gradient_loss_workspace(long long nplanes, int H, int W, size_t* bytes);
+int srmi_gradient_loss_parts(const float* pred, const float* target, long long nplanes, int H, int W, float eps,
+                             float* parts, float* cparts, void* workspace, size_t workspace_bytes, void* stream);
+int srmi_gradient_loss_from_parts(const float* parts, const float* cparts, long long nplanes, float weight,
+                                  const float* base, float* grad4, float* total, void* stream);
+int srmi_gradient_loss_dy(const float* pred, const float* target, long long nplanes, int H, int W, float eps,
+                          float weight, const float* grad4, float* dy, void* stream);
 
 /* ---- training batch preparation ------------------ */
 /* raw [B][C][T][T] fp32 tiles (select_batch, sres/base/source/swot/raw.py:160-166)

@@ -183,6 +183,13 @@ _SIGS = {
                                      C.c_int),
     "srmi_quantile_map_fit": ([P, P, C.c_int, C.c_int, F, C.c_longlong, P, P, P, P], C.c_int),
     "srmi_quantile_map_apply": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, P, P], C.c_int),
+    "srmi_gradient_workspace": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_gradient": ([P, P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, P, C.c_size_t, P, P, P, P, P, P],
+                      C.c_int),
+    "srmi_gradient_loss_workspace": ([C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_gradient_loss_parts": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, P, P, P, C.c_size_t, P], C.c_int),
+    "srmi_gradient_loss_from_parts": ([P, P, C.c_longlong, C.c_float, P, P, P, P], C.c_int),
+    "srmi_gradient_loss_dy": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_float, P, P, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

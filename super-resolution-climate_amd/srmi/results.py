@@ -38,6 +38,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .gradient_names import GRADIENT_STATS
+
 STRUCTURES = ("tiles", "image")  # ResultStructure values (sres/controller/config.py:3-5)
 
 
@@ -332,6 +334,78 @@ def load_ssim(path: str) -> Tuple[Dict[str, np.ndarray], List[str]]:
         if "map" in f.variables:
             out["map"] = np.array(f.variables["map"][:], dtype=np.float32)
         return out, names.split(",") if names else []
+
+
+GRADIENT_SCALARS = GRADIENT_STATS  # srmi.gradient_names: the order of srmi_gradient's stats columns
+GRADIENT_MAPS = ("gmag_pred", "gmag_truth")
+
+
+def save_gradient(path: str, gradient: Dict[str, object], varnames: Sequence[str], spacing=(1.0, 1.0)) -> str:
+    """One gradient score (the dict of srmi.gradient.GradientScore.measure, e.g. one entry of
+    RegionSuperResolver.score_gradient's third result) as a netCDF-3 file, through the same
+    scipy writer: 'mean_pred', 'mean_truth', 'sharpness', 'rmse_mag', 'rmse_vec', 'cosine' as
+    float64 with ``_FillValue = NaN`` and 'count' as float64 (netCDF-3 has no int64; a double
+    holds every count below 2^53 exactly) on ('channel',), 'sums' as float64 on ('channel',
+    'sum') when the dict holds it, 'gmag_pred' / 'gmag_truth' as float32 on ('channel', 'y',
+    'x') with ``_FillValue = NaN`` when the dict holds them, and the attributes ``varnames``
+    (the channel names joined by ``,``) and ``spacing`` (dy, dx).  A 'distribution' entry is
+    not written: save_distribution takes it.  No reference counterpart."""
+    from scipy.io import netcdf_file
+    missing = [k for k in GRADIENT_SCALARS + ("count",) if k not in gradient]
+    if missing:
+        raise ValueError(f"gradient lacks {missing}")
+    n = len(varnames)
+    maps = [q for q in GRADIENT_MAPS if q in gradient]
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        f.spacing = np.array([float(v) for v in spacing], dtype=np.float64)
+        f.createDimension("channel", n)
+        for q in GRADIENT_SCALARS + ("count",):
+            a = np.ascontiguousarray(_np(gradient[q]).astype(np.float64))
+            if a.shape != (n,):
+                raise ValueError(f"{q}: {a.shape} is not {(n,)}")
+            dv = f.createVariable(q, np.float64, ("channel",))
+            if q != "count":
+                dv._FillValue = np.array([np.nan], dtype=np.float64)
+            dv[:] = a
+        if "sums" in gradient:
+            a = np.ascontiguousarray(_np(gradient["sums"]).astype(np.float64))
+            if a.ndim != 2 or a.shape[0] != n:
+                raise ValueError(f"sums: {a.shape} is not [{n}, 7]")
+            f.createDimension("sum", a.shape[1])
+            dv = f.createVariable("sums", np.float64, ("channel", "sum"))
+            dv._FillValue = np.array([np.nan], dtype=np.float64)
+            dv[:] = a
+        for i, q in enumerate(maps):
+            m = np.ascontiguousarray(_np(gradient[q]).astype(np.float32))
+            if m.ndim != 3 or m.shape[0] != n:
+                raise ValueError(f"{q}: {m.shape} is not [{n}, H, W]")
+            if i == 0:
+                f.createDimension("y", m.shape[1])
+                f.createDimension("x", m.shape[2])
+            mv = f.createVariable(q, np.float32, ("channel", "y", "x"))
+            mv._FillValue = np.array([np.nan], dtype=np.float32)
+            mv[:] = m
+    return path
+
+
+def load_gradient(path: str) -> Tuple[Dict[str, np.ndarray], List[str], Tuple[float, float]]:
+    """The inverse of save_gradient: (the score as numpy arrays, 'count' int64 again; varnames;
+    spacing)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        out = {q: np.array(f.variables[q][:], dtype=np.float64) for q in GRADIENT_SCALARS}
+        out["count"] = np.array(f.variables["count"][:]).astype(np.int64)
+        if "sums" in f.variables:
+            out["sums"] = np.array(f.variables["sums"][:], dtype=np.float64)
+        for q in GRADIENT_MAPS:
+            if q in f.variables:
+                out[q] = np.array(f.variables[q][:], dtype=np.float32)
+        sp = np.atleast_1d(np.array(f.spacing, dtype=np.float64))
+        return out, names.split(",") if names else [], (float(sp[0]), float(sp[1]))
 
 
 DISTRIBUTION_SCALARS = ("pss", "w1", "under", "over")

@@ -110,7 +110,7 @@ from __future__ import annotations
 
 import math
 import numbers
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 
@@ -384,6 +384,7 @@ class RegionSuperResolver:
         self._spectra = {}  # (window, stride) -> the SpectralScore of each image (score_spectra)
         self._ssim = {}  # (data_range, maps) -> the SSIMScore of each image (score_ssim)
         self._distribution = {}  # (bins, joint, probs, value_range) -> the DistributionScore of each image
+        self._gradient = {}  # (spacing, maps, distribution) -> (GradientScore, DistributionScore | None) of each image
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -626,6 +627,66 @@ class RegionSuperResolver:
                                                                value_range, device=self.device)
                                        for name in ("model", "interpolated")}
         return images, losses, {name: sc.measure(images[name], hr) for name, sc in self._distribution[key].items()}
+
+    def score_gradient(self, hr_region: torch.Tensor, spacing=(1.0, 1.0), maps: bool = False, distribution=None):
+        """``score``, then the gradient score (srmi.gradient.GradientScore) of 'model' and of
+        'interpolated' against hr_region: (images, losses, {'model': ..., 'interpolated':
+        ...}), each entry the dict of GradientScore.measure -- per channel 'count' (the used
+        positions), 'mean_pred', 'mean_truth' (the mean Sobel gradient magnitudes, in the
+        field's units per unit of ``spacing`` = (dy, dx)), 'sharpness' (their ratio: below 1
+        the fronts are too smooth), 'rmse_mag', 'rmse_vec', 'cosine' (1: every front points
+        as the truth's does), 'sums', and with maps=True 'gmag_pred', 'gmag_truth' [C, s h,
+        s w], NaN where a position is not used.
+
+        distribution: None, or dict(bins=256, joint=32, value_range=None): each entry gains
+        'distribution', srmi.distribution.DistributionScore.measure run on the two magnitude
+        maps (their NaN are its mask), whose 'joint' table srmi.distribution.contingency turns
+        into hits, misses, false alarms, CSI and frequency bias of fronts above a threshold.
+        The maps are then produced (and returned) whether or not maps=True.
+
+        images and losses are ``score``'s, bit for bit; the entries are views valid until the
+        next call with the same arguments.  No host synchronisation.  With graph=True the
+        score is measured after the replay, outside the captured graph.
+
+        land=True: the NaN of the image and of hr_region are the mask -- a position whose 3 x
+        3 window touches one is not used, so a coast costs a one-pixel rim."""
+        from .distribution import DistributionScore
+        from .gradient import GradientScore, check_spacing
+        s = self.s
+        check_spacing(spacing)
+        dcfg = None
+        if distribution is not None:
+            if not isinstance(distribution, Mapping):
+                raise ValueError(f"distribution: a dict(bins=, joint=, value_range=) or None, got {distribution!r}")
+            extra = set(distribution) - {"bins", "joint", "value_range"}
+            if extra:
+                raise ValueError(f"distribution: unknown keys {sorted(extra)}")
+            vr = distribution.get("value_range")
+            try:
+                dcfg = (int(distribution.get("bins", 256)), int(distribution.get("joint", 32)),
+                        None if vr is None else tuple(float(v) for v in vr))
+            except (TypeError, ValueError):
+                raise ValueError(f"distribution {dict(distribution)!r}: bins and joint whole numbers, value_range "
+                                 "None or a (lo, hi) pair") from None
+        key = (tuple(float(v) for v in spacing), bool(maps), dcfg)
+        shape = (self.C, self.h * s, self.w * s)
+        if tuple(hr_region.shape) != shape:
+            raise ValueError(f"region shape {tuple(hr_region.shape)} != {shape}")
+        if key not in self._gradient:  # before the region is inferred: the constructors refuse bad arguments
+            self._gradient[key] = {
+                name: (GradientScore(shape, spacing, bool(maps) or dcfg is not None, device=self.device),
+                       DistributionScore(shape, dcfg[0], dcfg[1], value_range=dcfg[2], device=self.device)
+                       if dcfg is not None else None)
+                for name in ("model", "interpolated")}
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        out = {}
+        for name, (gs, ds) in self._gradient[key].items():
+            res = dict(gs.measure(images[name], hr))
+            if ds is not None:
+                res["distribution"] = ds.measure(res["gmag_pred"], res["gmag_truth"])
+            out[name] = res
+        return images, losses, out
 
     def fit_quantile_map(self, hr_regions, bins: int = 256, on: str = "detail", value_range=None,
                          tail_count: int = 16):

@@ -32,6 +32,7 @@ from .engine import (Engine, NetSpec, adam_step, adam_step_guarded, axpy, downsa
 from .consistency import ConsistencyLayer
 from .optim import check_clip_norm, check_ema, check_guard, ema_decay_at, make_lr_schedule
 from .spectra import SpectralLoss, check_spectral_loss_config
+from .gradient import GRADIENT_WINDOW, GradientLoss, check_gradient_loss_config
 from .ssim import SSIM_WINDOW, SSIMLoss, check_ssim_loss_config
 from .superres import check_consistent
 
@@ -79,7 +80,7 @@ class FusedTrainer:
                  cu_budget: Optional[int] = None, task=None, dp_reducer_stream: bool = False,
                  land: bool = False, spectral: Optional[Mapping] = None, consistent: int = 0,
                  clip_norm: Optional[float] = None, guard: Optional[bool] = None, ema: Optional[Mapping] = None,
-                 lr_schedule=None, ssim: Optional[Mapping] = None):
+                 lr_schedule=None, ssim: Optional[Mapping] = None, gradient: Optional[Mapping] = None):
         """task: the task config section (default: the active srmi ConfigContext's,
         if any).  apply_network's target selection is followed: when
         task.target_variables names fewer channels than the input, the loss target is
@@ -118,6 +119,17 @@ class FusedTrainer:
         Positions whose window touches a non-finite pixel are not used, so land=True needs
         nothing more.  Unknown keys, a bad weight (finite, >= 0) or range, or an HR tile below
         11 pixels (the window) in either dimension raise ValueError here.
+        gradient (no reference counterpart; DESIGN.md §1 "Gradient loss"): None, or the
+        configuration of a gradient loss term, dict(weight=1.0, eps=1e-6)
+        (srmi.gradient.GradientLoss's arguments; a missing key takes that default).  The
+        step's loss is then loss_fn (+ the spectral term) (+ the SSIM term) + weight * L_grad,
+        L_grad the mean over the used positions of the global batch of sqrt(Gx[e]^2 + Gy[e]^2 +
+        eps), e = sr - target and Gx, Gy the Sobel derivative at unit scale; its gradient is
+        added to the upstream gradient after the SSIM term's and before the consistency
+        layer's adjoint.  Positions whose 3 x 3 window touches a non-finite pixel are not
+        used, so land=True needs nothing more.  A non-dict, unknown keys, a bad weight
+        (finite, >= 0) or eps (finite, > 0), or an HR tile below 3 pixels in either dimension
+        raise ValueError here.  step() then also returns "pixel_loss" and "gradient_loss".
         consistent (no reference counterpart; DESIGN.md §1 "Consistency in training"): K in
         0 .. 16.  K > 0 makes K steps of back-projection onto the LR input the model's last,
         parameter-free layer (srmi.consistency.ConsistencyLayer): the network's output is
@@ -211,6 +223,18 @@ class FusedTrainer:
                 raise ValueError(f"ssim loss window {SSIM_WINDOW} larger than the HR tile "
                                  f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
             ssim_cfg = dict(weight=sw, data_range=sdr)
+        gradient_cfg = None
+        if gradient is not None:
+            if not isinstance(gradient, Mapping):
+                raise ValueError(f"gradient: a dict(weight=, eps=) or None, got {gradient!r}")
+            extra = set(gradient) - {"weight", "eps"}
+            if extra:
+                raise ValueError(f"gradient: unknown keys {sorted(extra)}")
+            gw, geps = check_gradient_loss_config(gradient.get("weight", 1.0), gradient.get("eps", 1e-6))
+            if min(lr_hw) * spec.scale < GRADIENT_WINDOW:
+                raise ValueError(f"gradient loss window {GRADIENT_WINDOW} larger than the HR tile "
+                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
+            gradient_cfg = dict(weight=gw, eps=geps)
         self.info = info or DistInfo()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.tindx = None if tindx is None else torch.tensor(tindx, dtype=torch.long, device=self.device)
@@ -256,11 +280,11 @@ class FusedTrainer:
                    if interp_loss else None)
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
         # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
-        # (a spectral or an SSIM term: always -- its gradient is added to the pixel loss's)
+        # (a spectral, SSIM or gradient term: always -- its gradient is added to the pixel loss's)
         # (a consistency layer: always -- its adjoint runs on it)
         self.dy = (torch.empty_like(self.sr)
                    if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None
-                   or ssim_cfg is not None or self.consistent
+                   or ssim_cfg is not None or gradient_cfg is not None or self.consistent
                    else None)
         # the consistency layer and, with land, the LR batch as it was before the flood fill
         self.layer = (ConsistencyLayer((batch, C, h, w), s, self.umode, self.dmode, self.consistent, self.device)
@@ -296,6 +320,10 @@ class FusedTrainer:
         # used-position counts of the GLOBAL batch, which travel as the spectral term's do
         self.ssim = (SSIMLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **ssim_cfg)
                      if ssim_cfg is not None else None)
+        # the gradient term: its workgroups' partial sums, and the per-plane sums and
+        # used-position counts of the GLOBAL batch, which travel as the SSIM term's do
+        self.gradient = (GradientLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **gradient_cfg)
+                         if gradient_cfg is not None else None)
         self.streams = [None] + [engine_stream(self.device) for _ in range(micro - 1)]
         self.dp_staged = not dp_reducer_stream
         self.reducer = GradReducer(self.eng.table, spec.arch, spec.nlayers, self.info, self.device,
@@ -416,6 +444,11 @@ class FusedTrainer:
             if self.info.enabled:
                 for v in self.ssim.views():
                     v.zero_()
+        if self.gradient is not None:
+            self.gradient.set_global_batch(gb)
+            if self.info.enabled:
+                for v in self.gradient.views():
+                    v.zero_()
         for st in self.streams[1:]:
             st.wait_stream(main)
         # forward + loss partials per micro-batch (an empty micro-batch adds nothing)
@@ -442,6 +475,8 @@ class FusedTrainer:
                     self.spectral.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
                 if self.ssim is not None:
                     self.ssim.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
+                if self.gradient is not None:
+                    self.gradient.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
                 if self.interp_loss:  # self.loss(btarget, binterp), dual_trainer.py:316-317
                     up = upsample(self.lrbuf[sl], s, out=self.up[sl], mode=self.umode)
                     itgt = hr[sl] if self.tgt_b is None else self.tgt_b[sl]
@@ -457,12 +492,18 @@ class FusedTrainer:
             if self.info.enabled:
                 allreduce_sum_(self.ssim.gparts[:2 * gb * self.ssim.C], self.info)
             self.ssim.finalize(self.loss4[3:4] if self.spectral is None else self.spectral.total)
+        if self.gradient is not None:  # chained behind whichever term came last
+            if self.info.enabled:
+                allreduce_sum_(self.gradient.gparts[:2 * gb * self.gradient.C], self.info)
+            self.gradient.finalize(self.ssim.total if self.ssim is not None
+                                   else self.spectral.total if self.spectral is not None else self.loss4[3:4])
         for st in self.streams[1:]:
             st.wait_stream(main)
-        # the upstream gradient from the finalised loss, zero on land; with a spectral or SSIM term
+        # the upstream gradient from the finalised loss, zero on land; with a spectral, SSIM or gradient term
         # or a consistency layer the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then
         # the terms' on top
-        explicit = self.spectral is not None or self.ssim is not None or self.layer is not None
+        explicit = (self.spectral is not None or self.ssim is not None or self.gradient is not None
+                    or self.layer is not None)
         if self.land or (explicit and self.loss_kind == SRMI_LOSS_RMSE):
             for k in range(self.micro):
                 sl = sls[k]
@@ -483,6 +524,12 @@ class FusedTrainer:
                 if sl.stop > sl.start:
                     with self._ctx(k):
                         self.ssim.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
+        if self.gradient is not None:
+            for k in range(self.micro):
+                sl = sls[k]
+                if sl.stop > sl.start:
+                    with self._ctx(k):
+                        self.gradient.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
         if self.layer is not None:  # through the layer's adjoint: dy becomes the network output's gradient
             for k in range(self.micro):
                 sl = sls[k]
@@ -582,6 +629,8 @@ class FusedTrainer:
             out = {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
         if self.ssim is not None:
             out.update(loss=self.ssim.total, pixel_loss=self.loss4[3:4], ssim_loss=self.ssim.ssim4[3:4])
+        if self.gradient is not None:
+            out.update(loss=self.gradient.total, pixel_loss=self.loss4[3:4], gradient_loss=self.gradient.grad4[3:4])
         if self.guard:
             out["grad_norm"] = self.ctl[0:1]
             out["step_skipped"] = self.ctl[2:3]

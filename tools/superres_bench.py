@@ -46,6 +46,15 @@ time of the numpy oracle (tests/ssim_oracle.py, fp64 and fp32) on the host for t
 pairs of fields, run once, with the device's largest deviation from the fp64 oracle next to
 e32, the fp32 oracle's; writes profiles/ssim_bench.json.  No pass / fail bar.
 
+--gradient: what does the gradient score cost?  The same arrangement with ``score_gradient``
+and GradientScore.measure: ``score``, ``score_gradient`` (with and without the maps) and the
+stage alone alternate window by window.  The bytes the stage must move are both fields read
+once per measure plus the two magnitude maps written when asked for (gradient_stage_bytes);
+they are reported with the bytes/s they make and the time they take at --hbm-tbs (the
+achievable HBM rate): a floor computed from shapes, not measured.  The numpy oracle
+(tests/gradient_oracle.py) runs once on the host for the counts and the largest deviation of
+the map; writes profiles/gradient_bench.json.  No pass / fail bar.
+
 --distribution: what does the distribution score cost, and on which data?  One
 RegionSuperResolver at the last of --overlaps scores a synthetic HR truth: ``score``,
 ``score_distribution`` and, window by window in turn on one device, the score's launches alone
@@ -351,6 +360,95 @@ def ssim_main(a, spec, params, dev, kw):
            "stage_gb_per_s": {k: round(v / (med[k] * 1e-3) / 1e9, 1) for k, v in nbytes.items()},
            "scores": scores, "nwin": int(ssim["model"]["nwin"].item()),
            "host_oracle_s": {k: round(v, 2) for k, v in host.items()},
+           "device_map_vs_oracle_max_abs": {k: float(f"{v:.3e}") for k, v in dev_err.items()},
+           "e32_map_max_abs": {k: float(f"{v:.3e}") for k, v in e32s.items()}}
+    return res
+
+
+def gradient_stage_bytes(px: float) -> dict:
+    """The bytes the two measures (model, interpolated) of one call must move: both fields read
+    once, plus the two magnitude maps written when asked for (fp32)."""
+    return {"stage": 2 * 2 * 4 * px, "stage_maps": 2 * 4 * 4 * px}
+
+
+def gradient_main(a, spec, params, dev, kw):
+    import time
+
+    import numpy as np
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.superres import RegionSuperResolver
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gradient_oracle as go
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    hr = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    rs = RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                             graph=not a.no_graph, **kw)
+    for _ in range(a.warmup):
+        images, losses, grad = rs.score_gradient(hr, maps=True)
+        rs.score_gradient(hr)
+    torch.cuda.synchronize()
+    names = ("model", "interpolated")
+    sp = (1.0, 1.0)
+    scorers = {True: rs._gradient[(sp, True, None)], False: rs._gradient[(sp, False, None)]}
+
+    def stage(maps):
+        for name in names:
+            scorers[maps][name][0].measure(images[name], hr)
+
+    runs = {"score": lambda: rs.score(hr), "score_gradient": lambda: rs.score_gradient(hr),
+            "score_gradient_maps": lambda: rs.score_gradient(hr, maps=True), "stage": lambda: stage(False),
+            "stage_maps": lambda: stage(True)}
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for k, fn in runs.items():
+            n = a.regions * (20 if k.startswith("stage") else 1)  # a window of the stage alone is many calls
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(n):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / n)
+    images, losses, grad = rs.score_gradient(hr, maps=True)
+    torch.cuda.synchronize()
+    truth = hr.cpu().numpy()
+    host, dev_err, e32s, scores = 0.0, {}, {}, {}
+    for name in names:
+        img = images[name].cpu().numpy()
+        t0 = time.perf_counter()
+        o64 = go.score(img, truth)
+        host += time.perf_counter() - t0
+        o32 = go.score(img, truth, dtype=np.float32)
+        if int(grad[name]["count"].item()) != int(o64["count"][0]):
+            raise SystemExit(f"superres_bench: {name}: count differs from the oracle's")
+        got = grad[name]["gmag_pred"].cpu().numpy().astype(np.float64)
+        dev_err[name] = float(np.nanmax(np.abs(got - o64["gmag_pred"])))
+        e32s[name] = float(np.nanmax(np.abs(o32["gmag_pred"].astype(np.float64) - o64["gmag_pred"])))
+        scores[name] = {q: float(grad[name][q]) for q in go.STATS}
+        scores[name]["rmse_of_score"] = float(losses[name])
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    nbytes = gradient_stage_bytes(float(side) ** 2)
+    res = {"tool": "superres_bench --gradient", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64 score_gradient, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR tile "
+                                  f"{a.tile}, overlap {r}; two gradient scores (model, interpolated) per call",
+                      "network": "untrained (seeded initial weights, synthetic fields)",
+                      "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                      "regions_per_window": a.regions, "stage_calls_per_window": a.regions * 20,
+                      "workspace_mib_per_score": round(scorers[True]["model"][0].workspace.numel() / 2 ** 20, 2),
+                      "hbm_tbs": a.hbm_tbs},
+           "ms": {k: {"median": round(med[k], 4), "min_max": [round(min(v), 4), round(max(v), 4)]}
+                  for k, v in ms.items()},
+           "stage_share_of_score_gradient": round(med["stage"] / med["score_gradient"], 5),
+           "stage_maps_share_of_score_gradient_maps": round(med["stage_maps"] / med["score_gradient_maps"], 5),
+           "stage_over_score": round(med["stage"] / med["score"], 5),
+           "score_gradient_over_score": round(med["score_gradient"] / med["score"], 4),
+           "stage_bytes": {k: int(v) for k, v in nbytes.items()},
+           "stage_gb_per_s": {k: round(v / (med[k] * 1e-3) / 1e9, 1) for k, v in nbytes.items()},
+           "stage_memory_floor_ms": {k: round(v / (a.hbm_tbs * 1e12) * 1e3, 4) for k, v in nbytes.items()},
+           "stage_time_over_floor": {k: round(med[k] / (v / (a.hbm_tbs * 1e12) * 1e3), 2) for k, v in nbytes.items()},
+           "scores": scores, "count": int(grad["model"]["count"].item()), "host_oracle_fp64_s": round(host, 2),
            "device_map_vs_oracle_max_abs": {k: float(f"{v:.3e}") for k, v in dev_err.items()},
            "e32_map_max_abs": {k: float(f"{v:.3e}") for k, v in e32s.items()}}
     return res
@@ -763,6 +861,8 @@ def main():
     ap.add_argument("--spectra", type=int, nargs="?", const=256, default=None, metavar="WINDOW",
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
     ap.add_argument("--ssim", action="store_true", help="time score_ssim's SSIM stage beside score")
+    ap.add_argument("--gradient", action="store_true", help="time score_gradient's stage beside score")
+    ap.add_argument("--hbm-tbs", type=float, default=6.3, help="achievable HBM rate the memory floor is taken at")
     ap.add_argument("--distribution", action="store_true",
                     help="time score_distribution's stage beside score and the SSIM stage, on a smooth and a white input")
     ap.add_argument("--ensemble", type=int, nargs="+", default=None, metavar="K", choices=(1, 4, 8),
@@ -772,20 +872,22 @@ def main():
     ap.add_argument("--quantile-map", action="store_true",
                     help="time the quantile map's launches and the region with the map on and off, and score both")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
-                                                "spectra_bench.json, ssim_bench.json, distribution_bench.json, "
+                                                "spectra_bench.json, ssim_bench.json, gradient_bench.json, "
+                                                "distribution_bench.json, "
                                                 "ensemble_bench.json, consistency_bench.json, "
                                                 "quantile_map_bench.json)")
     a = ap.parse_args()
     if (sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution
-            + a.quantile_map > 1):
-        raise SystemExit("superres_bench: --land, --spectra, --ssim, --distribution, --ensemble, --consistent and "
-                         "--quantile-map are separate runs")
+            + a.quantile_map + a.gradient > 1):
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --gradient, --distribution, --ensemble, "
+                         "--consistent and --quantile-map are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "superres_land_bench.json" if a.land is not None else
                              "spectra_bench.json" if a.spectra is not None else
                              "ssim_bench.json" if a.ssim else
+                             "gradient_bench.json" if a.gradient else
                              "distribution_bench.json" if a.distribution else
                              "ensemble_bench.json" if a.ensemble is not None else
                              "consistency_bench.json" if a.consistent is not None else
@@ -806,10 +908,11 @@ def main():
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
     if (a.land is not None or a.spectra is not None or a.ssim or a.distribution or a.ensemble is not None
-            or a.consistent is not None or a.quantile_map):
+            or a.consistent is not None or a.quantile_map or a.gradient):
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
                           ssim_main(a, spec, params, dev, kw) if a.ssim else
+                          gradient_main(a, spec, params, dev, kw) if a.gradient else
                           distribution_main(a, spec, params, dev, kw) if a.distribution else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
                           quantile_map_main(a, spec, params, dev, kw) if a.quantile_map else
