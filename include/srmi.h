@@ -1016,8 +1016,10 @@ int srmi_consistency_adjoint_apply(const float* Q, const int* active, int C, int
  * gradient windows of the used jobs, tapered and not yet scaled, and the used flags stay
  * in the workspace for srmi_spectral_loss_dy.
  * srmi_spectral_loss_from_parts: parts and cparts summed over the nplanes of the (global)
- * batch in a fixed order, spec4 = {S, Nused, 1 / (Nused P), L_spec} (all 0 when Nused = 0)
- * and total[0] = fma(weight, spec4[3], loss4[3]); loss4 (a finalised pixel loss) is only read.
+ * batch in fp64 in a fixed grouping (that of srmi_gradient_loss_from_parts below), spec4 =
+ * {S, Nused, 1 / (Nused P), L_spec} (all 0 when Nused = 0) and total[0] = fma(weight, spec4[3],
+ * base[0]).  base: one device float, the finalised pixel loss (&loss4[3]), as its siblings
+ * below take it; it is only read.
  * srmi_spectral_loss_dy: dy [nplanes][H][W] = fma(weight * spec4[2], the fp32 sum of the used
  * windows' gradients covering the pixel in ascending window index, dy); the scale is read
  * from the device.  A pixel no used window covers is not written; weight == 0 launches nothing.
@@ -1029,7 +1031,7 @@ int srmi_spectral_loss_parts(const float* pred, const float* target, long long n
                              float eps, float* parts, float* cparts, void* workspace, size_t workspace_bytes,
                              void* stream);
 int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
-                                  const float* loss4, float* spec4, float* total, void* stream);
+                                  const float* base, float* spec4, float* total, void* stream);
 int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long long nplanes, int H, int W, int P, int Q,
                           float weight, const float* spec4, float* dy, void* stream);
 
@@ -1068,9 +1070,10 @@ int srmi_spectral_loss_dy(const void* workspace, size_t workspace_bytes, long lo
  * rounded once to fp32; cparts[nplanes]: their count as a float (exact: H W <= 2^24).  Every
  * element of the workspace that srmi_ssim_loss_dy reads is written here.
  * srmi_ssim_loss_from_parts: parts and cparts [nplanes] summed over the planes of the
- * (global) batch in fp64 in plane order; ssim4 = {S, Nused, 1 / Nused, L_ssim} (all 0 when
- * Nused = 0) and total[0] = fma(weight, ssim4[3], base[0]).  base: one device float, the
- * finalised pixel loss (&loss4[3]) or the spectral term's total; it is only read.
+ * (global) batch in fp64 in a fixed grouping (that of srmi_gradient_loss_from_parts below);
+ * ssim4 = {S, Nused, 1 / Nused, L_ssim} (all 0 when Nused = 0) and total[0] = fma(weight,
+ * ssim4[3], base[0]).  base: one device float, the finalised pixel loss (&loss4[3]) or the
+ * total of the term before this one; it is only read.
  * srmi_ssim_loss_dy: workspace as srmi_ssim_loss_parts left it for these planes, pred and
  * target the same fields; dy [nplanes][H][W] = fma(-weight ssim4[2], dS / da, dy), the scale
  * read from the device, one rounding.  A pixel that is not finite in both pred and target is
@@ -1117,9 +1120,11 @@ int srmi_ssim_loss_dy(const void* workspace, size_t workspace_bytes, const float
  * srmi_gradient_loss_from_parts: parts and cparts [nplanes] summed over the planes of the
  * (global) batch in fp64 in a fixed grouping -- 256 contiguous shares of ceil(nplanes / 256)
  * planes, each in plane order, then the shares in order: the plain sum in plane order up to
- * 256 planes, and for any nplanes independent of how the planes were split over calls; grad4 = {S, Nused, 1 / Nused, L_grad} (all 0 when
- * Nused = 0) and total[0] = fma(weight, grad4[3], base[0]).  base: one device float, the total
- * of the terms before this one; it is only read.
+ * 256 planes, and for any nplanes independent of how the planes were split over calls (the
+ * three terms' finalizes are one piece of device code); grad4 = {S, Nused, 1 / Nused, L_grad}
+ * (all 0 when Nused = 0) and total[0] = fma(weight, grad4[3], base[0]).  base: one device
+ * float, the finalised pixel loss (&loss4[3]) or the total of the term before this one; it is
+ * only read.
  * srmi_gradient_loss_dy: dy [nplanes][H][W] = fma(weight grad4[2], dS / dpred, dy), the scale
  * read from the device, one rounding, one writer per pixel.  It RECOMPUTES U and V from pred
  * and target (a workgroup stages its rectangle of e with a two-pixel halo in LDS) and so takes

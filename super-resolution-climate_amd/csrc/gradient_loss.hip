@@ -15,10 +15,9 @@
 //       or outside the plane), forms a, b and phi at its pixels and writes its sum and count
 //       (fp64 / integer, a fixed tree).
 //   gradient_loss_plane_kernel  one workgroup per plane: the tile sums in a fixed order,
-//       rounded once into parts, the count into cparts.
-//   gradient_loss_finalize_kernel  parts and cparts over the planes of the global batch, fp64:
-//       256 contiguous shares each summed in plane order, then the shares in order (the plain
-//       sum in plane order up to 256 planes): grad4 and total.
+//       rounded once into parts, the count into cparts (loss_term.hpp's term_plane_reduce).
+//   gradient_loss_finalize_kernel  parts and cparts over the planes of the global batch
+//       (loss_term.hpp's term_finalize): grad4 and total.
 //   gradient_loss_dy_kernel     one workgroup per rectangle of pixels: stages e with a
 //       two-pixel halo, forms U = a / phi and V = b / phi on the one-pixel halo (0 where the
 //       position is not used) in LDS and gathers Gx^T U + Gy^T V = -(Gx[U] + Gy[V]), the
@@ -38,6 +37,7 @@
 
 #include "common.hpp"
 #include "gradient_common.hpp"
+#include "loss_term.hpp"
 #include "srmi_internal.hpp"
 
 namespace srmi {
@@ -118,16 +118,7 @@ __global__ void __launch_bounds__(kGradThreads) gradient_loss_tile_kernel(const 
       ++n;
     }
   }
-  red[tid] = s;
-  redc[tid] = n;
-  __syncthreads();
-  for (int w = kGradThreads / 2; w > 0; w >>= 1) {
-    if (tid < w) {
-      red[tid] += red[tid + w];
-      redc[tid] += redc[tid + w];
-    }
-    __syncthreads();
-  }
+  term_tree(s, n, red, redc, tid);
   if (tid == 0) {
     char* pws = ws + (size_t)plane * plan.stride;
     reinterpret_cast<double*>(pws)[t] = red[0];
@@ -135,41 +126,13 @@ __global__ void __launch_bounds__(kGradThreads) gradient_loss_tile_kernel(const 
   }
 }
 
-// parts[plane] = the tile sums, cparts[plane] = the tile counts: thread l sums its contiguous
-// share of the plane's tiles in tile order, then a fixed tree over the 256 shares
 __global__ void __launch_bounds__(kGradThreads) gradient_loss_plane_kernel(const char* __restrict__ ws,
                                                                            GradLossPlan plan,
                                                                            float* __restrict__ parts,
                                                                            float* __restrict__ cparts) {
-  __shared__ double red[kGradThreads];
-  __shared__ int redc[kGradThreads];
-  const int plane = blockIdx.x, tid = threadIdx.x;
-  const char* pws = ws + (size_t)plane * plan.stride;
-  const double* psum = reinterpret_cast<const double*>(pws);
-  const int* pcnt = reinterpret_cast<const int*>(pws + plan.off_pcnt);
-  const int n = plan.tiles_per_plane;
-  const int share = (n + kGradThreads - 1) / kGradThreads;
-  const int t0 = min(tid * share, n), t1 = min(t0 + share, n);
-  double s = 0.0;
-  int c = 0;
-  for (int t = t0; t < t1; ++t) {
-    s += psum[t];
-    c += pcnt[t];
-  }
-  red[tid] = s;
-  redc[tid] = c;
-  __syncthreads();
-  for (int w = kGradThreads / 2; w > 0; w >>= 1) {
-    if (tid < w) {
-      red[tid] += red[tid + w];
-      redc[tid] += redc[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    parts[plane] = (float)red[0];
-    cparts[plane] = (float)redc[0];  // <= H W <= 2^24: exact
-  }
+  const char* pws = ws + (size_t)blockIdx.x * plan.stride;
+  term_plane_reduce(reinterpret_cast<const double*>(pws), reinterpret_cast<const int*>(pws + plan.off_pcnt),
+                    plan.tiles_per_plane, blockIdx.x, parts, cparts);
 }
 
 __global__ void __launch_bounds__(kGradThreads) gradient_loss_finalize_kernel(const float* __restrict__ parts,
@@ -177,37 +140,7 @@ __global__ void __launch_bounds__(kGradThreads) gradient_loss_finalize_kernel(co
                                                                               long long nplanes, float weight,
                                                                               const float* base, float* grad4,
                                                                               float* total) {
-  __shared__ double sums[kGradThreads], counts[kGradThreads];
-  const int tid = threadIdx.x;
-  const long long share = (nplanes + kGradThreads - 1) / kGradThreads;
-  const long long i0 = min(tid * share, nplanes), i1 = min(i0 + share, nplanes);
-  double s = 0.0, n = 0.0;
-  for (long long i = i0; i < i1; ++i) {
-    s += (double)parts[i];
-    n += (double)cparts[i];
-  }
-  sums[tid] = s;
-  counts[tid] = n;
-  __syncthreads();
-  if (tid != 0) return;
-  s = 0.0;
-  n = 0.0;
-  for (int i = 0; i < kGradThreads; ++i) {  // the shares are contiguous and taken in order: a fixed grouping
-    s += sums[i];
-    n += counts[i];
-  }
-  const float b0 = base[0];
-  float l = 0.0f;
-  if (n > 0.0) {
-    l = (float)(s / n);
-    grad4[0] = (float)s;
-    grad4[1] = (float)n;
-    grad4[2] = (float)(1.0 / n);
-    grad4[3] = l;
-  } else {  // no used position: the term and its gradient are 0, not NaN
-    grad4[0] = grad4[1] = grad4[2] = grad4[3] = 0.0f;
-  }
-  total[0] = __fmaf_rn(weight, l, b0);
+  term_finalize<false>(parts, cparts, nplanes, 1.0, weight, base, grad4, total);  // L_grad = S / Nused
 }
 
 template <bool Vec>

@@ -21,8 +21,8 @@
 //       A_k are summed per thread in bin order and over the threads by a tree, in fp64.
 //   spectral_loss_plane_kernel   per plane the job sums in window order (fp64, rounded
 //       once) and the used-job count into parts / cparts.
-//   spectral_loss_finalize_kernel  parts and cparts over the planes in a fixed order
-//       (256 contiguous shares in plane order, then the 256 sums in order), fp64.
+//   spectral_loss_finalize_kernel  parts and cparts over the planes of the global batch
+//       (loss_term.hpp's term_finalize): spec4 and total.
 //   spectral_loss_dy_kernel      a thread per pixel adds the used windows covering it in
 //       ascending window index (fp32) and then scale * sum to dy: every pixel has one
 //       writer and one order, whatever the grid.  A pixel no used window covers is not
@@ -38,6 +38,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "loss_term.hpp"
 #include "spectra_fft.hpp"
 #include "srmi_internal.hpp"
 
@@ -275,37 +276,8 @@ __global__ void __launch_bounds__(kSpecThreads) spectral_loss_plane_kernel(const
 
 __global__ void __launch_bounds__(kSpecThreads) spectral_loss_finalize_kernel(
     const float* __restrict__ parts, const float* __restrict__ cparts, long long nplanes, int P, float weight,
-    const float* __restrict__ loss4, float* __restrict__ spec4, float* __restrict__ total) {
-  __shared__ double sums[kSpecThreads], counts[kSpecThreads];
-  const int tid = threadIdx.x;
-  const long long share = (nplanes + kSpecThreads - 1) / kSpecThreads;
-  const long long i0 = min(tid * share, nplanes), i1 = min(i0 + share, nplanes);
-  double s = 0.0, n = 0.0;
-  for (long long i = i0; i < i1; ++i) {
-    s += (double)parts[i];
-    n += (double)cparts[i];
-  }
-  sums[tid] = s;
-  counts[tid] = n;
-  __syncthreads();
-  if (tid != 0) return;
-  s = 0.0;
-  n = 0.0;
-  for (int i = 0; i < kSpecThreads; ++i) {
-    s += sums[i];
-    n += counts[i];
-  }
-  float l = 0.0f;
-  if (n > 0.0) {
-    l = (float)(s / (n * (double)P));
-    spec4[0] = (float)s;
-    spec4[1] = (float)n;
-    spec4[2] = (float)(1.0 / (n * (double)P));
-    spec4[3] = l;
-  } else {  // no used job: the term and its gradient are 0, not NaN
-    spec4[0] = spec4[1] = spec4[2] = spec4[3] = 0.0f;
-  }
-  total[0] = __fmaf_rn(weight, l, loss4[3]);
+    const float* base, float* spec4, float* total) {
+  term_finalize<false>(parts, cparts, nplanes, (double)P, weight, base, spec4, total);  // L_spec = S / (Nused P)
 }
 
 __global__ void __launch_bounds__(kSpecThreads) spectral_loss_dy_kernel(const char* __restrict__ ws, SpecLossPlan plan,
@@ -391,13 +363,13 @@ int srmi_spectral_loss_parts(const float* pred, const float* target, long long n
 }
 
 int srmi_spectral_loss_from_parts(const float* parts, const float* cparts, long long nplanes, int P, float weight,
-                                  const float* loss4, float* spec4, float* total, void* stream) {
-  if (!parts || !cparts || !loss4 || !spec4 || !total || nplanes < 1 || (P != 16 && P != 32 && P != 64) ||
+                                  const float* base, float* spec4, float* total, void* stream) {
+  if (!parts || !cparts || !base || !spec4 || !total || nplanes < 1 || (P != 16 && P != 32 && P != 64) ||
       !(weight >= 0.0f) || !std::isfinite(weight))
     return SRMI_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(spectral_loss_finalize_kernel, dim3(1), dim3(kSpecThreads), 0, st, parts, cparts, nplanes, P,
-                     weight, loss4, spec4, total);
+                     weight, base, spec4, total);
   SRMI_CHECK_LAUNCH();
   return 0;
 }

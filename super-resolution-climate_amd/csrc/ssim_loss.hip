@@ -24,11 +24,10 @@
 //       0), runs the horizontal 11-tap pass for the five moment planes and the flag count into
 //       LDS and the vertical pass into registers, evaluates ssim and A, B, C, writes the three
 //       coefficients of its positions and its sum and count (fp64 / integer, a fixed tree).
-//   ssim_loss_plane_kernel   one workgroup per plane: the tile sums in a fixed order (256
-//       contiguous shares in tile order, then a fixed tree), rounded once into parts, the
-//       count into cparts.
-//   ssim_loss_finalize_kernel  parts and cparts over the planes of the global batch in plane
-//       order, fp64: ssim4 and total.
+//   ssim_loss_plane_kernel   one workgroup per plane: the tile sums in a fixed order, rounded
+//       once into parts, the count into cparts (loss_term.hpp's term_plane_reduce).
+//   ssim_loss_finalize_kernel  parts and cparts over the planes of the global batch
+//       (loss_term.hpp's term_finalize): ssim4 and total.
 //   ssim_loss_dy_kernel      one workgroup per kTileH x kTileW rectangle of PIXELS: stages the
 //       34 x 74 positions whose windows reach it (0 outside the map: the full correlation),
 //       filters A, B and C with the same separable taps, and adds scale (G^T A + a' G^T B + b'
@@ -46,6 +45,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "loss_term.hpp"
 #include "srmi_internal.hpp"
 #include "ssim_common.hpp"
 
@@ -193,56 +193,19 @@ __global__ void __launch_bounds__(kSsimThreads, 2) ssim_loss_tile_kernel(const f
   }
 
   // ---- the workgroup's sum and count, a fixed tree (stage was last read before the barrier above)
-  red[tid] = s_ssim;
-  redc[tid] = nwin;
-  __syncthreads();
-  for (int o = kSsimThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[tid] += red[tid + o];
-      redc[tid] += redc[tid + o];
-    }
-    __syncthreads();
-  }
+  term_tree(s_ssim, nwin, red, redc, tid);
   if (tid == 0) {
     reinterpret_cast<double*>(pws + plan.off_psum)[t] = red[0];
     reinterpret_cast<int*>(pws + plan.off_pcnt)[t] = redc[0];
   }
 }
 
-// parts[plane] = the tile sums, cparts[plane] = the tile counts: thread l sums its contiguous
-// share of the plane's tiles in tile order, then a fixed tree over the 256 shares
 __global__ void __launch_bounds__(kSsimThreads) ssim_loss_plane_kernel(const char* __restrict__ ws, SsimLossPlan plan,
                                                                        float* __restrict__ parts,
                                                                        float* __restrict__ cparts) {
-  __shared__ double red[kSsimThreads];
-  __shared__ int redc[kSsimThreads];
-  const int plane = blockIdx.x, tid = threadIdx.x;
-  const char* pws = ws + (size_t)plane * plan.stride;
-  const double* psum = reinterpret_cast<const double*>(pws + plan.off_psum);
-  const int* pcnt = reinterpret_cast<const int*>(pws + plan.off_pcnt);
-  const int n = plan.tiles_per_plane;
-  const int share = (n + kSsimThreads - 1) / kSsimThreads;
-  const int t0 = min(tid * share, n), t1 = min(t0 + share, n);
-  double s = 0.0;
-  int c = 0;
-  for (int t = t0; t < t1; ++t) {
-    s += psum[t];
-    c += pcnt[t];
-  }
-  red[tid] = s;
-  redc[tid] = c;
-  __syncthreads();
-  for (int o = kSsimThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[tid] += red[tid + o];
-      redc[tid] += redc[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    parts[plane] = (float)red[0];
-    cparts[plane] = (float)redc[0];  // <= H W <= 2^24: exact
-  }
+  const char* pws = ws + (size_t)blockIdx.x * plan.stride;
+  term_plane_reduce(reinterpret_cast<const double*>(pws + plan.off_psum),
+                    reinterpret_cast<const int*>(pws + plan.off_pcnt), plan.tiles_per_plane, blockIdx.x, parts, cparts);
 }
 
 __global__ void __launch_bounds__(kSsimThreads) ssim_loss_finalize_kernel(const float* __restrict__ parts,
@@ -250,37 +213,7 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_loss_finalize_kernel(const 
                                                                           long long nplanes, float weight,
                                                                           const float* base, float* ssim4,
                                                                           float* total) {
-  __shared__ double sums[kSsimThreads], counts[kSsimThreads];
-  const int tid = threadIdx.x;
-  const long long share = (nplanes + kSsimThreads - 1) / kSsimThreads;
-  const long long i0 = min(tid * share, nplanes), i1 = min(i0 + share, nplanes);
-  double s = 0.0, n = 0.0;
-  for (long long i = i0; i < i1; ++i) {
-    s += (double)parts[i];
-    n += (double)cparts[i];
-  }
-  sums[tid] = s;
-  counts[tid] = n;
-  __syncthreads();
-  if (tid != 0) return;
-  s = 0.0;
-  n = 0.0;
-  for (int i = 0; i < kSsimThreads; ++i) {  // the shares are contiguous: this is plane order
-    s += sums[i];
-    n += counts[i];
-  }
-  const float b0 = base[0];
-  float l = 0.0f;
-  if (n > 0.0) {
-    l = (float)(1.0 - s / n);
-    ssim4[0] = (float)s;
-    ssim4[1] = (float)n;
-    ssim4[2] = (float)(1.0 / n);
-    ssim4[3] = l;
-  } else {  // no used position: the term and its gradient are 0, not NaN
-    ssim4[0] = ssim4[1] = ssim4[2] = ssim4[3] = 0.0f;
-  }
-  total[0] = __fmaf_rn(weight, l, b0);
+  term_finalize<true>(parts, cparts, nplanes, 1.0, weight, base, ssim4, total);  // L_ssim = 1 - S / Nused
 }
 
 __global__ void __launch_bounds__(kSsimThreads, 2) ssim_loss_dy_kernel(const char* __restrict__ ws, SsimLossPlan plan,

@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from ._lib import SRMI_ERR_ARG, call, load, ptr, stream_handle
+from .loss_term import LossTerm
 from .gradient_names import GRADIENT_STATS, GRADIENT_SUMS  # noqa: F401  (the one copy of the column order)
 
 GRADIENT_WINDOW = 3
@@ -140,7 +141,7 @@ def check_gradient_loss_config(weight, eps) -> Tuple[float, float]:
     return weight, eps
 
 
-class GradientLoss:
+class GradientLoss(LossTerm):
     """The gradient loss term of a training step (no reference counterpart; the definition is
     srmi.h's "gradient loss term", tests/gradient_oracle.py restates it in fp64): ``L_grad = S /
     Nused``, S the sum of sqrt(Gx[e]^2 + Gy[e]^2 + eps), e = pred - target, over the used
@@ -156,100 +157,31 @@ class GradientLoss:
         finalize(base)                       once the parts of the global batch are in place
         add_dy(dy, pred, target, rows=...)   dy += weight * d L_grad / d pred
 
+    (srmi.loss_term.LossTerm's protocol; finalize leaves grad4 = {S, Nused, 1 / Nused, L_grad}
+    and total = base[0] + weight * L_grad, base the total of the terms before this one).
     Nothing allocates or reads back: all three can be captured, and every result is
     bit-identical from run to run and independent of how the batch is split over calls."""
 
+    name, record, window = "gradient", "grad4", GRADIENT_WINDOW
+    DEFAULTS = dict(weight=1.0, eps=1e-6)
+
+    @staticmethod
+    def check_config(weight, eps) -> Dict[str, object]:
+        weight, eps = check_gradient_loss_config(weight, eps)
+        return dict(weight=weight, eps=eps)
+
     def __init__(self, shape: Sequence[int], weight: float = 1.0, eps: float = 1e-6,
                  device: Optional[torch.device] = None, global_batch: Optional[int] = None):
-        self.weight, self.eps = check_gradient_loss_config(weight, eps)
-        N, Cn, H, W = (int(v) for v in shape)
-        if N < 1 or Cn < 1:
-            raise ValueError(f"gradient loss over a batch {tuple(shape)}")
-        self.N, self.C, self.H, self.W = N, Cn, H, W
-        n = C.c_size_t()
-        rc = load().srmi_gradient_loss_workspace(N * Cn, H, W, C.byref(n))
-        if rc == SRMI_ERR_ARG:
-            raise ValueError(f"gradient loss needs planes of H, W >= {GRADIENT_WINDOW} (the window) with H W <= 2^24, "
-                             f"got {(H, W)}")
-        if rc:
-            raise RuntimeError(f"srmi_gradient_loss_workspace: {rc}")
-        self.plane_bytes = int(n.value) // (N * Cn)
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        d = self.device
-        self.workspace = torch.empty(int(n.value), dtype=torch.uint8, device=d)
-        self.gcap = N if global_batch is None else int(global_batch)
-        if self.gcap < N:
-            raise ValueError(f"global batch {self.gcap} smaller than the batch {N}")
-        # [parts | cparts] of the gb <= gcap tiles of a step, gb * C each (one all-reduce)
-        self.gparts = torch.zeros(2 * self.gcap * Cn, dtype=torch.float32, device=d)
-        self.gb = self.gcap
-        self.grad4 = torch.zeros(4, dtype=torch.float32, device=d)
-        self.total = torch.zeros(1, dtype=torch.float32, device=d)
+        super().__init__(shape, dict(weight=weight, eps=eps), device, global_batch)
 
-    def _rows(self, n: int, rows) -> int:
-        r0 = 0 if rows is None else int(rows.start or 0) if isinstance(rows, slice) else int(rows)
-        if isinstance(rows, slice) and rows.stop is not None and rows.stop - r0 != n:
-            raise ValueError(f"rows {rows} for {n} tiles")
-        if r0 < 0 or n < 1 or r0 + n > self.N:
-            raise ValueError(f"tiles {r0} .. {r0 + n - 1} outside the batch of {self.N}")
-        return r0
-
-    def _check(self, name: str, t: torch.Tensor) -> None:
-        if (t.dim() != 4 or tuple(t.shape[1:]) != (self.C, self.H, self.W) or t.dtype != torch.float32
-                or not t.is_contiguous()):
-            raise ValueError(f"{name}: a contiguous fp32 [n, {self.C}, {self.H}, {self.W}] tensor is needed, got "
-                             f"{tuple(t.shape)} {t.dtype}")
-
-    def set_global_batch(self, gb: int) -> None:
-        """The tiles of this step's global batch (<= global_batch): where cparts begins."""
-        if not 1 <= gb <= self.gcap:
-            raise ValueError(f"global batch {gb} outside 1 .. {self.gcap}")
-        self.gb = int(gb)
-
-    def views(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(parts, cparts) of the step's global batch, gb * C each, adjacent."""
-        n = self.gb * self.C
-        return self.gparts[:n], self.gparts[n:2 * n]
-
-    def parts(self, pred: torch.Tensor, target: torch.Tensor, rows=None, global_row: Optional[int] = None) -> None:
-        """The sums of phi and the used counts of pred / target [n, C, H, W]: tiles rows ..
-        rows + n - 1 of this object's batch (their part of the workspace), tiles global_row ..
-        of the global batch (their rows of parts / cparts; default: the same)."""
-        self._check("pred", pred)
-        self._check("target", target)
-        n = pred.shape[0]
-        if target.shape[0] != n:
-            raise ValueError(f"pred of {n} tiles, target of {target.shape[0]}")
-        r0 = self._rows(n, rows)
-        g0 = r0 if global_row is None else int(global_row)
-        if g0 < 0 or g0 + n > self.gb:
-            raise ValueError(f"tiles {g0} .. {g0 + n - 1} outside the global batch of {self.gb}")
-        parts, cparts = self.views()
-        ws = self.workspace[r0 * self.C * self.plane_bytes:]
-        call("srmi_gradient_loss_parts", ptr(pred), ptr(target), n * self.C, self.H, self.W, self.eps,
-             ptr(parts[g0 * self.C:]), ptr(cparts[g0 * self.C:]), ptr(ws), n * self.C * self.plane_bytes,
-             torch.cuda.current_stream(self.device).cuda_stream)
-
-    def finalize(self, base: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """grad4 = {S, Nused, 1 / Nused, L_grad} of the global batch's parts and counts and
-        total = base[0] + weight * L_grad; base (one device float: the total of the terms
-        before this one) is only read."""
-        parts, cparts = self.views()
-        call("srmi_gradient_loss_from_parts", ptr(parts), ptr(cparts), self.gb * self.C, self.weight, ptr(base),
-             ptr(self.grad4), ptr(self.total), torch.cuda.current_stream(self.device).cuda_stream)
-        return {"grad4": self.grad4, "total": self.total, "gradient_loss": self.grad4[3:4]}
+    def _parts_args(self):
+        return (self.eps,)
 
     def add_dy(self, dy: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, rows=None) -> None:
         """dy [n, C, H, W] (holding the upstream gradient so far) += weight * grad4[2] * dS / d
         pred, recomputed from pred / target (nothing ``parts`` stored is read; rows is checked
         only).  weight == 0, or a pixel that is not finite in pred and in target: its bits
         stay."""
-        self._check("dy", dy)
-        self._check("pred", pred)
-        self._check("target", target)
-        n = dy.shape[0]
-        if pred.shape[0] != n or target.shape[0] != n:
-            raise ValueError(f"dy of {n} tiles, pred of {pred.shape[0]}, target of {target.shape[0]}")
-        self._rows(n, rows)
+        n, _ = self._check_dy(dy, pred, target, rows)
         call("srmi_gradient_loss_dy", ptr(pred), ptr(target), n * self.C, self.H, self.W, self.eps, self.weight,
-             ptr(self.grad4), ptr(dy), torch.cuda.current_stream(self.device).cuda_stream)
+             ptr(self.grad4), ptr(dy), self._stream())

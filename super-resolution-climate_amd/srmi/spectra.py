@@ -35,6 +35,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from ._lib import SRMI_ERR_ARG, call, load, ptr, stream_handle
+from .loss_term import LossTerm
 
 QUANTITIES = ("power_pred", "power_truth", "power_error", "cross")
 
@@ -115,7 +116,7 @@ def check_spectral_loss_config(window, stride, eps, weight) -> Tuple[int, int, f
     return P, int(stride), eps, weight
 
 
-class SpectralLoss:
+class SpectralLoss(LossTerm):
     """The spectral loss term of a training step (no reference counterpart; the definition
     is srmi.h's "spectral loss term", tests/spectral_loss_oracle.py restates it in fp64):
     with d = pred - target on every window of side ``window`` at stride ``stride`` of every
@@ -128,103 +129,52 @@ class SpectralLoss:
     steps are, as in FusedTrainer:
 
         parts(pred, target, rows=...)   per micro-batch, after the forward
-        finalize(loss4)                 once the parts of the global batch are in place
+        finalize(base)                  once the parts of the global batch are in place
         add_dy(dy, rows=...)            dy += weight * d L_spec / d pred
+
+    (srmi.loss_term.LossTerm's protocol; finalize leaves spec4 = {S, Nused, 1 / (Nused window),
+    L_spec} and total = base[0] + weight * L_spec).
 
     Nothing allocates or reads back: all three can be captured, and every result is
     bit-identical from run to run and independent of how the batch is split over calls.
     The taper is 0 at its first point, so the first row and column of a plane get no
     spectral gradient (the last ones nearly none): the pixel loss covers them."""
 
+    name, record = "spectral", "spec4"
+    DEFAULTS = dict(weight=1.0, window=64, stride=32, eps=1e-12)
+
+    @staticmethod
+    def check_config(weight, window, stride, eps) -> Dict[str, object]:
+        P, Q, eps, weight = check_spectral_loss_config(window, stride, eps, weight)
+        return dict(weight=weight, window=P, stride=Q, eps=eps)
+
     def __init__(self, shape: Sequence[int], window: int = 64, stride: Optional[int] = 32, eps: float = 1e-12,
                  weight: float = 1.0, device: Optional[torch.device] = None, global_batch: Optional[int] = None):
-        self.window, self.stride, self.eps, self.weight = check_spectral_loss_config(window, stride, eps, weight)
-        N, Cn, H, W = (int(v) for v in shape)
-        if N < 1 or Cn < 1:
-            raise ValueError(f"spectral loss over a batch {tuple(shape)}")
-        self.N, self.C, self.H, self.W = N, Cn, H, W
-        n = C.c_size_t()
-        rc = load().srmi_spectral_loss_workspace(N * Cn, H, W, self.window, self.stride, C.byref(n))
-        if rc == SRMI_ERR_ARG:
-            raise ValueError(f"spectral loss window {self.window} at stride {self.stride} does not fit planes of "
-                             f"{(H, W)}")
-        if rc:
-            raise RuntimeError(f"srmi_spectral_loss_workspace: {rc}")
-        self.plane_bytes = int(n.value) // (N * Cn)
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        d = self.device
-        self.workspace = torch.empty(int(n.value), dtype=torch.uint8, device=d)
-        self.gcap = N if global_batch is None else int(global_batch)
-        if self.gcap < N:
-            raise ValueError(f"global batch {self.gcap} smaller than the batch {N}")
-        # [parts | cparts] of the gb <= gcap tiles of a step, gb * C each (one all-reduce)
-        self.gparts = torch.zeros(2 * self.gcap * Cn, dtype=torch.float32, device=d)
-        self.gb = self.gcap
-        self.spec4 = torch.zeros(4, dtype=torch.float32, device=d)
-        self.total = torch.zeros(1, dtype=torch.float32, device=d)
+        super().__init__(shape, dict(weight=weight, window=window, stride=stride, eps=eps), device, global_batch)
 
-    def _rows(self, n: int, rows) -> int:
-        r0 = 0 if rows is None else int(rows.start or 0) if isinstance(rows, slice) else int(rows)
-        if isinstance(rows, slice) and rows.stop is not None and rows.stop - r0 != n:
-            raise ValueError(f"rows {rows} for {n} tiles")
-        if r0 < 0 or n < 1 or r0 + n > self.N:
-            raise ValueError(f"tiles {r0} .. {r0 + n - 1} outside the batch of {self.N}")
-        return r0
+    def _plan_args(self):
+        return self.window, self.stride
 
-    def _check(self, name: str, t: torch.Tensor) -> None:
-        if (t.dim() != 4 or tuple(t.shape[1:]) != (self.C, self.H, self.W) or t.dtype != torch.float32
-                or not t.is_contiguous()):
-            raise ValueError(f"{name}: a contiguous fp32 [n, {self.C}, {self.H}, {self.W}] tensor is needed, got "
-                             f"{tuple(t.shape)} {t.dtype}")
+    def _parts_args(self):
+        return self.window, self.stride, self.eps
 
-    def set_global_batch(self, gb: int) -> None:
-        """The tiles of this step's global batch (<= global_batch): where cparts begins."""
-        if not 1 <= gb <= self.gcap:
-            raise ValueError(f"global batch {gb} outside 1 .. {self.gcap}")
-        self.gb = int(gb)
+    def _finalize_args(self):  # spec4[2] = 1 / (Nused window)
+        return self.window, self.weight
 
-    def views(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(parts, cparts) of the step's global batch, gb * C each, adjacent."""
-        n = self.gb * self.C
-        return self.gparts[:n], self.gparts[n:2 * n]
+    def _no_fit(self) -> str:
+        return f"spectral loss window {self.window} at stride {self.stride} does not fit planes of {(self.H, self.W)}"
 
-    def parts(self, pred: torch.Tensor, target: torch.Tensor, rows=None, global_row: Optional[int] = None) -> None:
-        """The parts and counts of pred / target [n, C, H, W]: tiles rows .. rows + n - 1 of
-        this object's batch (their part of the workspace), tiles global_row .. of the
-        global batch (their rows of parts / cparts; default: the same)."""
-        self._check("pred", pred)
-        self._check("target", target)
-        n = pred.shape[0]
-        if target.shape[0] != n:
-            raise ValueError(f"pred of {n} tiles, target of {target.shape[0]}")
-        r0 = self._rows(n, rows)
-        g0 = r0 if global_row is None else int(global_row)
-        if g0 < 0 or g0 + n > self.gb:
-            raise ValueError(f"tiles {g0} .. {g0 + n - 1} outside the global batch of {self.gb}")
-        parts, cparts = self.views()
-        ws = self.workspace[r0 * self.C * self.plane_bytes:]
-        call("srmi_spectral_loss_parts", ptr(pred), ptr(target), n * self.C, self.H, self.W, self.window, self.stride,
-             self.eps, ptr(parts[g0 * self.C:]), ptr(cparts[g0 * self.C:]), ptr(ws), n * self.C * self.plane_bytes,
-             torch.cuda.current_stream(self.device).cuda_stream)
-
-    def finalize(self, loss4: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """spec4 = {S, Nused, 1 / (Nused window), L_spec} of the global batch's parts and
-        total = loss4[3] + weight * L_spec; loss4 (the finalised pixel loss) is only read."""
-        parts, cparts = self.views()
-        call("srmi_spectral_loss_from_parts", ptr(parts), ptr(cparts), self.gb * self.C, self.window, self.weight,
-             ptr(loss4), ptr(self.spec4), ptr(self.total), torch.cuda.current_stream(self.device).cuda_stream)
-        return {"spec4": self.spec4, "total": self.total, "spectral_loss": self.spec4[3:4]}
-
-    def add_dy(self, dy: torch.Tensor, rows=None) -> None:
+    def add_dy(self, dy: torch.Tensor, pred=None, target=None, rows=None) -> None:
         """dy [n, C, H, W] (tiles rows .. of the batch, holding the pixel loss's upstream
-        gradient) += weight * spec4[2] * the used windows' gradients.  weight == 0, or no
-        used window over a pixel: its bits stay."""
+        gradient) += weight * spec4[2] * the used windows' gradients, which ``parts`` left in
+        the workspace: pred and target are not read.  weight == 0, or no used window over a
+        pixel: its bits stay."""
         self._check("dy", dy)
         n = dy.shape[0]
         r0 = self._rows(n, rows)
         ws = self.workspace[r0 * self.C * self.plane_bytes:]
         call("srmi_spectral_loss_dy", ptr(ws), n * self.C * self.plane_bytes, n * self.C, self.H, self.W, self.window,
-             self.stride, self.weight, ptr(self.spec4), ptr(dy), torch.cuda.current_stream(self.device).cuda_stream)
+             self.stride, self.weight, ptr(self.spec4), ptr(dy), self._stream())
 
 
 def effective_resolution(error_ratio, window: int, threshold: float = 0.5) -> Sequence[float]:

@@ -31,13 +31,32 @@ from .engine import (Engine, NetSpec, adam_step, adam_step_guarded, axpy, downsa
                      grad_norm_workspace, interp_size, upsample)
 from .consistency import ConsistencyLayer
 from .optim import check_clip_norm, check_ema, check_guard, ema_decay_at, make_lr_schedule
-from .spectra import SpectralLoss, check_spectral_loss_config
-from .gradient import GRADIENT_WINDOW, GradientLoss, check_gradient_loss_config
-from .ssim import SSIM_WINDOW, SSIMLoss, check_ssim_loss_config
+from .spectra import SpectralLoss
+from .gradient import GradientLoss
+from .ssim import SSIMLoss
 from .superres import check_consistent
 
 LOSS_KINDS = {"l2": SRMI_LOSS_RMSE, "charbonnier": SRMI_LOSS_MEAN}
 CHARBONNIER_EPS = 1e-6  # ModelTrainer.eps, sres/controller/dual_trainer.py:122
+
+
+def _term_config(cls, cfg, hr_hw) -> Optional[Dict[str, object]]:
+    """The checked configuration of the loss term ``cls`` (a srmi.loss_term.LossTerm) given to
+    FusedTrainer as ``<name>=cfg``, None for None; a missing key takes the term's default.
+    ValueError for what is not a dict, an unknown key, a value the term refuses, or a window
+    larger than the HR tile -- in this order, and before anything is allocated."""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, Mapping):
+        raise ValueError(f"{cls.name}: a dict({', '.join(f'{k}=' for k in cls.DEFAULTS)}) or None, got {cfg!r}")
+    extra = set(cfg) - set(cls.DEFAULTS)
+    if extra:
+        raise ValueError(f"{cls.name}: unknown keys {sorted(extra)}")
+    cfg = cls.check_config(**{**cls.DEFAULTS, **cfg})
+    window = cfg.get("window", cls.window)
+    if window > min(hr_hw):
+        raise ValueError(f"{cls.name} loss window {window} larger than the HR tile {tuple(hr_hw)}")
+    return cfg
 
 
 class _Null:
@@ -198,43 +217,11 @@ class FusedTrainer:
                              f"{spec.nchannels_in}-channel interpolated input does not broadcast (as in the reference)")
         self.loss_fn = loss_fn
         self.loss_kind = LOSS_KINDS[loss_fn]
-        spectral_cfg = None
-        if spectral is not None:
-            if not isinstance(spectral, Mapping):
-                raise ValueError(f"spectral: a dict(weight=, window=, stride=, eps=) or None, got {spectral!r}")
-            extra = set(spectral) - {"weight", "window", "stride", "eps"}
-            if extra:
-                raise ValueError(f"spectral: unknown keys {sorted(extra)}")
-            P, Q, seps, sw = check_spectral_loss_config(spectral.get("window", 64), spectral.get("stride", 32),
-                                                        spectral.get("eps", 1e-12), spectral.get("weight", 1.0))
-            if P > min(lr_hw) * spec.scale:
-                raise ValueError(f"spectral loss window {P} larger than the HR tile "
-                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
-            spectral_cfg = dict(window=P, stride=Q, eps=seps, weight=sw)
-        ssim_cfg = None
-        if ssim is not None:
-            if not isinstance(ssim, Mapping):
-                raise ValueError(f"ssim: a dict(weight=, data_range=) or None, got {ssim!r}")
-            extra = set(ssim) - {"weight", "data_range"}
-            if extra:
-                raise ValueError(f"ssim: unknown keys {sorted(extra)}")
-            sw, sdr = check_ssim_loss_config(ssim.get("weight", 1.0), ssim.get("data_range"))
-            if min(lr_hw) * spec.scale < SSIM_WINDOW:
-                raise ValueError(f"ssim loss window {SSIM_WINDOW} larger than the HR tile "
-                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
-            ssim_cfg = dict(weight=sw, data_range=sdr)
-        gradient_cfg = None
-        if gradient is not None:
-            if not isinstance(gradient, Mapping):
-                raise ValueError(f"gradient: a dict(weight=, eps=) or None, got {gradient!r}")
-            extra = set(gradient) - {"weight", "eps"}
-            if extra:
-                raise ValueError(f"gradient: unknown keys {sorted(extra)}")
-            gw, geps = check_gradient_loss_config(gradient.get("weight", 1.0), gradient.get("eps", 1e-6))
-            if min(lr_hw) * spec.scale < GRADIENT_WINDOW:
-                raise ValueError(f"gradient loss window {GRADIENT_WINDOW} larger than the HR tile "
-                                 f"{(lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)}")
-            gradient_cfg = dict(weight=gw, eps=geps)
+        # the configured loss terms in their fixed order: the order of step()'s chain
+        hr_hw = (lr_hw[0] * spec.scale, lr_hw[1] * spec.scale)
+        term_cfgs = [(cls, _term_config(cls, cfg, hr_hw))
+                     for cls, cfg in ((SpectralLoss, spectral), (SSIMLoss, ssim), (GradientLoss, gradient))]
+        term_cfgs = [(cls, cfg) for cls, cfg in term_cfgs if cfg is not None]
         self.info = info or DistInfo()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.tindx = None if tindx is None else torch.tensor(tindx, dtype=torch.long, device=self.device)
@@ -280,12 +267,10 @@ class FusedTrainer:
                    if interp_loss else None)
         # Charbonnier: the elementwise loss gradient is the backward's upstream gradient
         # (land: for the RMSE too -- zero on land, srmi_loss_dy_masked)
-        # (a spectral, SSIM or gradient term: always -- its gradient is added to the pixel loss's)
+        # (a loss term: always -- its gradient is added to the pixel loss's)
         # (a consistency layer: always -- its adjoint runs on it)
         self.dy = (torch.empty_like(self.sr)
-                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or spectral_cfg is not None
-                   or ssim_cfg is not None or gradient_cfg is not None or self.consistent
-                   else None)
+                   if self.loss_kind == SRMI_LOSS_MEAN or self.land or term_cfgs or self.consistent else None)
         # the consistency layer and, with land, the LR batch as it was before the flood fill
         self.layer = (ConsistencyLayer((batch, C, h, w), s, self.umode, self.dmode, self.consistent, self.device)
                       if self.consistent else None)
@@ -312,18 +297,13 @@ class FusedTrainer:
         # through the same single all-reduce (whole numbers: x + 0 and their sums are exact)
         self.gparts = torch.zeros((4 if self.land else 2) * self.gcap * TILE_LOSS_SUB, dtype=torch.float32,
                                   device=self.device)
-        # the spectral term: the gradient windows of this rank's tiles, and the per-plane
-        # parts and used-window counts of the GLOBAL batch, which travel as gparts does
-        self.spectral = (SpectralLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **spectral_cfg)
-                         if spectral_cfg is not None else None)
-        # the SSIM term: the coefficient maps of this rank's tiles, and the per-plane sums and
-        # used-position counts of the GLOBAL batch, which travel as the spectral term's do
-        self.ssim = (SSIMLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **ssim_cfg)
-                     if ssim_cfg is not None else None)
-        # the gradient term: its workgroups' partial sums, and the per-plane sums and
-        # used-position counts of the GLOBAL batch, which travel as the SSIM term's do
-        self.gradient = (GradientLoss(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **gradient_cfg)
-                         if gradient_cfg is not None else None)
+        # the loss terms: each owns a workspace for this rank's tiles (the spectral term's
+        # gradient windows, the SSIM term's coefficient maps, the gradient term's partial sums)
+        # and the per-plane parts and used counts of the GLOBAL batch, which travel as gparts does
+        self.terms = [cls(tuple(self.sr.shape), device=self.device, global_batch=self.gcap, **cfg)
+                      for cls, cfg in term_cfgs]
+        by_name = {t.name: t for t in self.terms}
+        self.spectral, self.ssim, self.gradient = (by_name.get(n) for n in ("spectral", "ssim", "gradient"))
         self.streams = [None] + [engine_stream(self.device) for _ in range(micro - 1)]
         self.dp_staged = not dp_reducer_stream
         self.reducer = GradReducer(self.eng.table, spec.arch, spec.nlayers, self.info, self.device,
@@ -434,20 +414,10 @@ class FusedTrainer:
             lcparts, icparts = self.gparts[m * n:m * n + n], self.gparts[m * n + n:m * n + 2 * n]
         if self.info.enabled:  # the other ranks' tiles' parts stay 0 here
             self.gparts[:(4 if self.land else 2) * n].zero_()
-        if self.spectral is not None:
-            self.spectral.set_global_batch(gb)
+        for term in self.terms:
+            term.set_global_batch(gb)
             if self.info.enabled:
-                for v in self.spectral.views():
-                    v.zero_()
-        if self.ssim is not None:
-            self.ssim.set_global_batch(gb)
-            if self.info.enabled:
-                for v in self.ssim.views():
-                    v.zero_()
-        if self.gradient is not None:
-            self.gradient.set_global_batch(gb)
-            if self.info.enabled:
-                for v in self.gradient.views():
+                for v in term.views():
                     v.zero_()
         for st in self.streams[1:]:
             st.wait_stream(main)
@@ -471,12 +441,8 @@ class FusedTrainer:
                 if self.dy is not None and not self.land:  # Charbonnier: the elementwise upstream gradient only
                     eng.charbonnier_partial(self.sr[sl], tgt[sl], None, count, CHARBONNIER_EPS, dy=self.dy[sl])
                 self._loss_parts(self.sr[sl], tgt[sl], lparts, t0 + sl.start, lcparts)
-                if self.spectral is not None:
-                    self.spectral.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
-                if self.ssim is not None:
-                    self.ssim.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
-                if self.gradient is not None:
-                    self.gradient.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
+                for term in self.terms:
+                    term.parts(self.sr[sl], tgt[sl], rows=sl.start, global_row=t0 + sl.start)
                 if self.interp_loss:  # self.loss(btarget, binterp), dual_trainer.py:316-317
                     up = upsample(self.lrbuf[sl], s, out=self.up[sl], mode=self.umode)
                     itgt = hr[sl] if self.tgt_b is None else self.tgt_b[sl]
@@ -484,26 +450,20 @@ class FusedTrainer:
         for st in self.streams[1:]:
             main.wait_stream(st)
         self._reduce_losses(gb, count, icount)
-        if self.spectral is not None:  # the term and its scale from the global batch's parts and counts
+        # each term and its scale from the global batch's parts and counts, chained: a term's
+        # total is the pixel loss + the terms before it + its own
+        prev = self.loss4[3:4] if self.terms else None
+        for term in self.terms:
             if self.info.enabled:
-                allreduce_sum_(self.spectral.gparts[:2 * gb * self.spectral.C], self.info)
-            self.spectral.finalize(self.loss4)
-        if self.ssim is not None:  # chained: its total is the pixel loss (+ the spectral term) + its own
-            if self.info.enabled:
-                allreduce_sum_(self.ssim.gparts[:2 * gb * self.ssim.C], self.info)
-            self.ssim.finalize(self.loss4[3:4] if self.spectral is None else self.spectral.total)
-        if self.gradient is not None:  # chained behind whichever term came last
-            if self.info.enabled:
-                allreduce_sum_(self.gradient.gparts[:2 * gb * self.gradient.C], self.info)
-            self.gradient.finalize(self.ssim.total if self.ssim is not None
-                                   else self.spectral.total if self.spectral is not None else self.loss4[3:4])
+                allreduce_sum_(term.gparts[:2 * gb * term.C], self.info)
+            term.finalize(prev)
+            prev = term.total
         for st in self.streams[1:]:
             st.wait_stream(main)
-        # the upstream gradient from the finalised loss, zero on land; with a spectral, SSIM or gradient term
-        # or a consistency layer the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then
+        # the upstream gradient from the finalised loss, zero on land; with a loss term or a
+        # consistency layer the RMSE's too ((p - t) * loss4[2], what the tail kernels form), then
         # the terms' on top
-        explicit = (self.spectral is not None or self.ssim is not None or self.gradient is not None
-                    or self.layer is not None)
+        explicit = bool(self.terms) or self.layer is not None
         if self.land or (explicit and self.loss_kind == SRMI_LOSS_RMSE):
             for k in range(self.micro):
                 sl = sls[k]
@@ -512,24 +472,12 @@ class FusedTrainer:
                         call("srmi_loss_dy_masked", ptr(self.sr[sl]), ptr(tgt[sl]), self.sr[sl].numel(),
                              self.loss_kind, CHARBONNIER_EPS, ptr(self.loss4), ptr(self.dy[sl]),
                              torch.cuda.current_stream(self.device).cuda_stream)
-        if self.spectral is not None:
+        for term in self.terms:
             for k in range(self.micro):
                 sl = sls[k]
                 if sl.stop > sl.start:
                     with self._ctx(k):
-                        self.spectral.add_dy(self.dy[sl], rows=sl.start)
-        if self.ssim is not None:
-            for k in range(self.micro):
-                sl = sls[k]
-                if sl.stop > sl.start:
-                    with self._ctx(k):
-                        self.ssim.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
-        if self.gradient is not None:
-            for k in range(self.micro):
-                sl = sls[k]
-                if sl.stop > sl.start:
-                    with self._ctx(k):
-                        self.gradient.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
+                        term.add_dy(self.dy[sl], self.sr[sl], tgt[sl], rows=sl.start)
         if self.layer is not None:  # through the layer's adjoint: dy becomes the network output's gradient
             for k in range(self.micro):
                 sl = sls[k]
@@ -622,15 +570,10 @@ class FusedTrainer:
                 eng.pack(self.params)
         for st in self.streams[1:]:
             main.wait_stream(st)
-        if self.spectral is not None:
-            out = {"loss": self.spectral.total, "interp_loss": self.iloss4[3:4], "pixel_loss": self.loss4[3:4],
-                   "spectral_loss": self.spectral.spec4[3:4]}
-        else:
-            out = {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
-        if self.ssim is not None:
-            out.update(loss=self.ssim.total, pixel_loss=self.loss4[3:4], ssim_loss=self.ssim.ssim4[3:4])
-        if self.gradient is not None:
-            out.update(loss=self.gradient.total, pixel_loss=self.loss4[3:4], gradient_loss=self.gradient.grad4[3:4])
+        out = {"loss": self.loss4[3:4], "interp_loss": self.iloss4[3:4]}
+        if self.terms:  # the last term's total is the step's loss
+            out.update(loss=self.terms[-1].total, pixel_loss=self.loss4[3:4])
+            out.update({f"{term.name}_loss": term.term4[3:4] for term in self.terms})
         if self.guard:
             out["grad_norm"] = self.ctl[0:1]
             out["step_skipped"] = self.ctl[2:3]

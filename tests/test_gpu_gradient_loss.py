@@ -315,6 +315,64 @@ def test_from_parts_chains_onto_a_given_base():
     assert rel_l2(res["dy"], 2.5 * ref["dy"].astype(np.float64)) < 4 * U
 
 
+# (the normaliser's multiplier m, the scalars before weight, whether l = 1 - S / (N m)) of srmi_<term>_loss_from_parts
+FROM_PARTS = {"spectral": (32.0, (32,), False), "ssim": (1.0, (), True), "gradient": (1.0, (), False)}
+
+
+def from_parts_expected(parts, cparts, m, one_minus, weight, base):
+    """srmi.h's order restated with Python floats (fp64, nothing fused): 256 contiguous shares of
+    ceil(nplanes / 256) planes, each summed left to right, then the 256 share sums left to right;
+    the record and l rounded to fp32 once each.  total = fma(weight, l, base): with weight 1 or
+    0.5 the product is exact, the fp64 sum of two fp32 values within 2^29 of each other is exact,
+    and one rounding to fp32 is left."""
+    n = len(parts)
+    share = -(-n // 256)
+    S = N = 0.0
+    for k in range(256):
+        s = c = 0.0
+        for i in range(min(k * share, n), min((k + 1) * share, n)):
+            s += float(parts[i])
+            c += float(cparts[i])
+        S += s
+        N += c
+    rec = np.zeros(4, np.float32)
+    if N > 0.0:
+        q = S / (N * m)
+        rec[:] = [S, N, 1.0 / (N * m), 1.0 - q if one_minus else q]
+    total = np.float32(float(np.float32(base)) + float(np.float32(weight)) * float(rec[3]))
+    return rec, total
+
+
+@pytest.mark.parametrize("nplanes", [1, 255, 256, 257, 1000])
+@pytest.mark.parametrize("term", list(FROM_PARTS))
+def test_from_parts_groups_the_planes_as_documented_bit_for_bit(term, nplanes):
+    """The three finalize launches on host-made parts (positive, of order 1) and counts (whole
+    numbers in 1 .. 2^20, or all zero): the record and the total are the bits of the host
+    restatement above, which never sees the code under test.  1, 255 and 256 planes are the plain
+    sum in plane order, 257 the first size with shares of two planes (and empty shares behind
+    them), 1000 shares of four with a ragged end."""
+    d = dev()
+    m, scalars, one_minus = FROM_PARTS[term]
+    f = getattr(_lib.load(), f"srmi_{term}_loss_from_parts")
+    rng = np.random.default_rng(1000 * list(FROM_PARTS).index(term) + nplanes)
+    parts = rng.uniform(0.5, 1.5, nplanes).astype(np.float32)
+    counts = rng.integers(1, 2 ** 20 + 1, nplanes).astype(np.float32)
+    for weight, base, cparts in ((1.0, 0.75, counts), (0.5, 1.2345678, counts), (1.0, 0.75, np.zeros_like(counts))):
+        l4 = torch.tensor([-7.0, -7.0, -7.0, base], device=d)  # a finalised pixel loss: [3] is the base
+        rec, tot = torch.full((4,), -7.0, device=d), torch.full((1,), -7.0, device=d)
+        pd, cd = torch.tensor(parts, device=d), torch.tensor(cparts, device=d)
+        assert f(ptr(pd), ptr(cd), nplanes, *scalars, weight, ptr(l4[3:4]), ptr(rec), ptr(tot), stream_handle()) == 0
+        torch.cuda.synchronize()
+        want_rec, want_tot = from_parts_expected(parts, cparts, m, one_minus, weight, base)
+        got_rec, got_tot = rec.cpu().numpy(), tot.cpu().numpy()
+        print(f"{term} nplanes={nplanes} weight={weight} N={want_rec[1]:.0f}: record {got_rec.tolist()} want "
+              f"{want_rec.tolist()}; total {got_tot[0]!r} want {want_tot!r}")
+        assert np.array_equal(nbits(got_rec), nbits(want_rec)), (weight, got_rec, want_rec)
+        assert nbits(got_tot)[0] == nbits(want_tot)[0], (weight, got_tot, want_tot)
+        assert cparts.any() or (not got_rec.any() and got_tot[0] == np.float32(base))  # no used position: 0, not NaN
+        assert np.array_equal(l4.cpu().numpy(), np.array([-7.0, -7.0, -7.0, base], np.float32))  # only read
+
+
 @pytest.mark.parametrize("shape,kind", [(SHAPES[0], "zero"), (SHAPES[3], "zero"), (SHAPES[3], "nan"), (SHAPES[5], "zero")],
                          ids=["3x3", "18x66", "18x66 nan", "192"])
 def test_one_plane_is_the_mean_of_phi_from_the_scores_path(shape, kind):
@@ -561,6 +619,21 @@ def test_all_terms_consistent_trainer_step_vs_oracle(monkeypatch):
     """Spectral + SSIM + gradient + consistent=2 against the composed oracle: the term chains
     onto the SSIM term's total, and its gradient enters before the layer's adjoint."""
     step_vs_oracle(monkeypatch, ro.synthetic_hr(3, 2, 192, 21), "l2", False, spectral=SPECTRAL, ssim=SSIM, consistent=2)
+
+
+def test_gradient_chains_onto_the_spectral_term_without_an_ssim_term(monkeypatch):
+    """The chain with a gap, spectral + gradient and no SSIM term, against the composed oracle
+    at the bars above: the gradient term's total is the spectral term's + weight * L_grad (one
+    fp32 fma; with weight 1 the fp64 sum of the two floats, rounded once), as the spectral
+    term's is the pixel loss + its own."""
+    tr, _, _ = step_vs_oracle(monkeypatch, ro.synthetic_hr(3, 2, 192, 21), "l2", False, spectral=SPECTRAL, ssim=None)
+    assert tr.ssim is None and [t.name for t in tr.terms] == ["spectral", "gradient"] and WEIGHT == 1.0
+    base, l, total = (float(v) for v in (tr.spectral.total, tr.gradient.grad4[3], tr.gradient.total))
+    want = np.float32(base + WEIGHT * l)
+    print(f"spectral total {base!r} + {WEIGHT} * L_grad {l!r} = {float(want)!r}, the gradient term's total {total!r}")
+    assert nbits(np.float32(total))[0] == nbits(want)[0]
+    spec_want = np.float32(float(tr.loss4[3]) + float(tr.spectral.weight) * float(tr.spectral.spec4[3]))
+    assert tr.spectral.weight == 1.0 and nbits(np.float32(base))[0] == nbits(spec_want)[0]
 
 
 # ------------------------------------------------------------- T3. the fp32 engine

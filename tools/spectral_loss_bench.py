@@ -87,7 +87,7 @@ def main():
     # the spectral launches alone, on the `on` trainer's own buffers
     tr = arms["on"]
     sl, dy = tr.spectral, torch.zeros_like(tr.sr)
-    stages = {"parts": lambda: sl.parts(tr.sr, hr), "finalize": lambda: sl.finalize(tr.loss4),
+    stages = {"parts": lambda: sl.parts(tr.sr, hr), "finalize": lambda: sl.finalize(tr.loss4[3:4]),
               "add_dy": lambda: sl.add_dy(dy)}
     stage_ms = {k: [] for k in stages}
     for name, fn in stages.items():
