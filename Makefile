@@ -6,7 +6,7 @@ SRC := $(PKG)/csrc
 OUT := $(PKG)/srmi/libsrmi.so
 OBJDIR ?= build/obj
 CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function -Iinclude $(EXTRA)
-HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip $(SRC)/gradient.hip $(SRC)/gradient_loss.hip
+HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip $(SRC)/gradient.hip $(SRC)/gradient_loss.hip $(SRC)/fss.hip
 CPPSRC := $(SRC)/engine.cpp
 OBJS := $(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIPSRC)) $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(CPPSRC))
 HDRS := $(wildcard $(SRC)/*.hpp) include/srmi.h

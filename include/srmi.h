@@ -114,6 +114,11 @@
  *   srmi_gradient_loss_dy        -> a term on the Sobel gradient of the error beside the pixel
  *                                   loss of a training step.  No reference counterpart: the
  *                                   reference trains on a pixel loss alone.
+ *   srmi_fss_workspace,
+ *   srmi_fss                     -> the fractions skill score: event fractions of a prediction
+ *                                   and of a truth in n x n neighbourhoods, for a ladder of n,
+ *                                   and the skilful scale.  No reference counterpart: the
+ *                                   reference scores a field by its RMSE alone.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -838,6 +843,59 @@ int srmi_gradient_workspace(int C, int H, int W, size_t* bytes);
 int srmi_gradient(const float* pred, const float* truth, int C, int H, int W, float inv_dy, float inv_dx,
                   void* workspace, size_t workspace_bytes, long long* count, double* sums, double* stats,
                   float* gmag_pred, float* gmag_truth, void* stream);
+
+/* ---- the fractions skill score (no reference counterpart) ---------------- */
+/* Is a feature of the truth there in the prediction, nearly in the right place, and how near?
+ * The fractions skill score (FSS, Roberts & Lean 2008) of the event "the value is at or above
+ * a threshold", for a ladder of neighbourhood sizes; tests/fss_oracle.py restates it in numpy.
+ *   Inputs: pred, truth [C][H][W] fp32 on the device, NaN / Inf allowed; thresholds [C][T] fp32
+ *   ON THE DEVICE (so that a device-side quantile can fill them without a host read), T in 1 ..
+ *   8; scales, a HOST array of N neighbourhood sizes n, N in 1 .. 16, each n odd, in 1 .. 255,
+ *   strictly increasing (passed to the kernels by value).
+ *   Per channel c.  Used pixel: finite in pred and in truth; used[c] is their count.  Event:
+ *   Ip(y, x) = used && pred >= thr[c][t], It(y, x) = used && truth >= thr[c][t], one fp32
+ *   comparison, so a NaN threshold gives no event; events[c][t] = {sum Ip, sum It}.
+ *   Window counts, h = (n - 1) / 2: Sp(y, x) = the sum of Ip over rows y - h .. y + h and columns
+ *   x - h .. x + h clipped to the plane -- what lies outside the plane or is not used is "no
+ *   event" in both fields (scipy.ndimage.uniform_filter(I, n, mode="constant") n^2, and pysteps'
+ *   convention for missing values); St the same of It.  Windows never cross planes.
+ *   Sums over ALL H W positions of the plane, int64: num[c][t][k] = sum (Sp - St)^2,
+ *   den[c][t][k] = sum (Sp^2 + St^2).  The n^4 of the fractions cancels: only integers are
+ *   summed, so every table is exact and the same bits from run to run.
+ *   derived [C][T][N + 6] fp64 = {fss[N], f_pred, f_truth, bias, target, afss, skilful}, formed
+ *   on the device from the integer tables alone: fss[k] = 1 - num / den (NaN when den == 0);
+ *   f_pred = ep / used, f_truth = et / used, bias = ep / et (IEEE: Inf or NaN when et == 0);
+ *   target = 0.5 + f_truth / 2, the "uniform" FSS and the usual bar for a skilful scale; afss =
+ *   2 ep et / (ep^2 + et^2), what fss tends to when the window covers the plane; skilful = the
+ *   smallest n of scales with fss >= target as a double, NaN when there is none.  A channel
+ *   without a used pixel has NaN in every derived entry and 0 in every table.
+ * Outputs on the device: num, den [C][T][N], events [C][T][2], used [C] int64; derived as above.
+ * Three launches on `stream`: events (one read of the fields; per 64-pixel row segment and
+ * threshold the wave's 64-bit ballot is the packed word of a bit plane in the workspace, bits
+ * past W zero; used and events from popcounts, as workgroup partials), windows (the grid covers
+ * channel x threshold x scale x tile, a tile 512 rows of one 64-pixel word column; the count of
+ * a row's events in columns x - h .. x + h is a popcount of at most five masked words and the
+ * window count slides down the rows, so the work per position does not depend on n; 64-bit
+ * accumulators), finish (the partials in plain sums, the tables and the derived values).  No
+ * global atomics, no host synchronisation, no allocation: capturable.
+ * srmi_fss_workspace (host only) gives the bytes of `workspace` (16-byte aligned; it need not
+ * be initialised): the 2 C T bit planes (rows padded by two words either side, which are never
+ * written and never counted), 17 uint32 per workgroup of the events launch, and two
+ * int64 per (channel, threshold, scale, tile).  pred, truth and thresholds have no alignment
+ * requirement.  A missing pointer, T or N or an n out of range, even or not increasing, a
+ * workspace that is too small or misaligned, C < 1, H or W < 1, H W > 2^31 - 1, or H W n_max^4 >
+ * 2^62 (the sums would leave int64; a 4096^2 plane at n = 255 is far inside): SRMI_ERR_ARG,
+ * nothing launched and no output touched.  launches: 0 for all three, or SRMI_FSS_* bits for
+ * some of them alone, in their order (for timing a launch by itself: a later launch reads what
+ * the earlier ones of a previous call left in the workspace); unknown bits: SRMI_ERR_ARG.
+ * Even n, thresholds on anomalies and a loss term are out of scope. */
+#define SRMI_FSS_EVENTS 1
+#define SRMI_FSS_WINDOWS 2
+#define SRMI_FSS_FINISH 4
+int srmi_fss_workspace(int C, int H, int W, int T, int N, size_t* bytes);
+int srmi_fss(const float* pred, const float* truth, int C, int H, int W, const float* thresholds, int T,
+             const int* scales, int N, void* workspace, size_t workspace_bytes, long long* num, long long* den,
+             long long* events, long long* used, double* derived, int launches, void* stream);
 
 /* ---- quantile mapping (no reference counterpart) ------------------------- */
 /* Empirical quantile mapping: a monotone transfer function T = F_truth^-1 o F_src, calibrated

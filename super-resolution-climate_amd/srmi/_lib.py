@@ -190,6 +190,9 @@ _SIGS = {
     "srmi_gradient_loss_parts": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, P, P, P, C.c_size_t, P], C.c_int),
     "srmi_gradient_loss_from_parts": ([P, P, C.c_longlong, C.c_float, P, P, P, P], C.c_int),
     "srmi_gradient_loss_dy": ([P, P, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_float, P, P, P], C.c_int),
+    "srmi_fss_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_fss": ([P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.POINTER(C.c_int), C.c_int, P, C.c_size_t, P, P, P, P, P,
+                  C.c_int, P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

@@ -408,6 +408,86 @@ def load_gradient(path: str) -> Tuple[Dict[str, np.ndarray], List[str], Tuple[fl
         return out, names.split(",") if names else [], (float(sp[0]), float(sp[1]))
 
 
+FSS_TABLES = ("num", "den")
+FSS_EVENTS = ("events_pred", "events_truth")
+FSS_SCALARS = ("f_pred", "f_truth", "bias", "target", "afss", "skilful_scale")  # srmi.fss.FSS_DERIVED
+
+
+def save_fss(path: str, fss: Dict[str, object], varnames: Sequence[str], thresholds, scales: Sequence[int]) -> str:
+    """One fractions skill score (the dict of srmi.fss.FractionsSkillScore.measure, e.g. one
+    entry of RegionSuperResolver.score_fss's third result) as a netCDF-3 file, through the same
+    scipy writer.  The integer tables -- 'num', 'den' on ('channel', 'threshold', 'scale'),
+    'events_pred', 'events_truth' on ('channel', 'threshold'), 'used' on ('channel',) -- are
+    written as PAIRS of int32, '<name>_hi' and '<name>_lo' (value = hi 2^32 + lo as unsigned):
+    netCDF-3 has no int64 and 'num' and 'den' pass 2^53, so a double would not hold them.
+    'fss' is float64 on ('channel', 'threshold', 'scale'), 'f_pred', 'f_truth', 'bias',
+    'target', 'afss', 'skilful_scale' float64 on ('channel', 'threshold'), all with
+    ``_FillValue = NaN``; 'thresholds' float32 on ('channel', 'threshold'); the coordinate
+    'scale' int32; the attribute ``varnames`` holds the channel names joined by ``,``.  No
+    reference counterpart."""
+    from scipy.io import netcdf_file
+    keys = FSS_TABLES + FSS_EVENTS + FSS_SCALARS + ("used", "fss")
+    missing = [k for k in keys if k not in fss]
+    if missing:
+        raise ValueError(f"fss lacks {missing}")
+    n, sc = len(varnames), np.asarray([int(v) for v in scales], dtype=np.int32)
+    thr = np.ascontiguousarray(_np(thresholds).astype(np.float32))
+    if thr.ndim != 2 or thr.shape[0] != n:
+        raise ValueError(f"thresholds: {thr.shape} is not [{n}, T]")
+    T, N = thr.shape[1], len(sc)
+    dims = {"used": ("channel",), "fss": ("channel", "threshold", "scale")}
+    dims.update({q: ("channel", "threshold", "scale") for q in FSS_TABLES})
+    dims.update({q: ("channel", "threshold") for q in FSS_EVENTS + FSS_SCALARS})
+    sizes = {"channel": n, "threshold": T, "scale": N}
+    arrays = {}
+    for q in keys:
+        a = _np(fss[q])
+        a = np.ascontiguousarray(a.astype(np.float64 if q in FSS_SCALARS + ("fss",) else np.int64))
+        shape = tuple(sizes[d] for d in dims[q])
+        if a.shape != shape:
+            raise ValueError(f"{q}: {a.shape} is not {shape}")
+        arrays[q] = a
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        for d, size in sizes.items():
+            f.createDimension(d, size)
+        sv = f.createVariable("scale", np.int32, ("scale",))
+        sv[:] = sc
+        tv = f.createVariable("thresholds", np.float32, ("channel", "threshold"))
+        tv._FillValue = np.array([np.nan], dtype=np.float32)
+        tv[:] = thr
+        for q in FSS_TABLES + FSS_EVENTS + ("used",):
+            u = arrays[q].view(np.uint64)
+            for part, half in (("hi", u >> np.uint64(32)), ("lo", u & np.uint64(0xFFFFFFFF))):
+                dv = f.createVariable(f"{q}_{part}", np.int32, dims[q])
+                dv[:] = half.astype(np.uint32).view(np.int32)
+        for q in FSS_SCALARS + ("fss",):
+            dv = f.createVariable(q, np.float64, dims[q])
+            dv._FillValue = np.array([np.nan], dtype=np.float64)
+            dv[:] = arrays[q]
+    return path
+
+
+def load_fss(path: str) -> Tuple[Dict[str, np.ndarray], List[str], np.ndarray, Tuple[int, ...]]:
+    """The inverse of save_fss: (the score as numpy arrays, the tables int64 again; varnames;
+    thresholds [C, T] fp32; scales)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        out = {}
+        for q in FSS_TABLES + FSS_EVENTS + ("used",):
+            hi = np.array(f.variables[f"{q}_hi"][:], dtype=np.int32).view(np.uint32).astype(np.uint64)
+            lo = np.array(f.variables[f"{q}_lo"][:], dtype=np.int32).view(np.uint32).astype(np.uint64)
+            out[q] = ((hi << np.uint64(32)) | lo).view(np.int64)
+        for q in FSS_SCALARS + ("fss",):
+            out[q] = np.array(f.variables[q][:], dtype=np.float64)
+        thr = np.array(f.variables["thresholds"][:], dtype=np.float32)
+        sc = tuple(int(v) for v in np.array(f.variables["scale"][:]))
+        return out, names.split(",") if names else [], thr, sc
+
+
 DISTRIBUTION_SCALARS = ("pss", "w1", "under", "over")
 DISTRIBUTION_QUANTILES = ("q_pred", "q_truth", "q_bias")
 DISTRIBUTION_TABLES = ("hist_pred", "hist_truth")

@@ -385,6 +385,7 @@ class RegionSuperResolver:
         self._ssim = {}  # (data_range, maps) -> the SSIMScore of each image (score_ssim)
         self._distribution = {}  # (bins, joint, probs, value_range) -> the DistributionScore of each image
         self._gradient = {}  # (spacing, maps, distribution) -> (GradientScore, DistributionScore | None) of each image
+        self._fss = {}  # (thresholds, probs, scales, on) -> the scorers of each image (score_fss)
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -685,6 +686,77 @@ class RegionSuperResolver:
             res = dict(gs.measure(images[name], hr))
             if ds is not None:
                 res["distribution"] = ds.measure(res["gmag_pred"], res["gmag_truth"])
+            out[name] = res
+        return images, losses, out
+
+    def score_fss(self, hr_region: torch.Tensor, thresholds=None, probs=(0.9, 0.99),
+                  scales=(1, 3, 5, 9, 17, 33, 65), on: str = "value"):
+        """``score``, then the fractions skill score (srmi.fss.FractionsSkillScore) of 'model' and
+        of 'interpolated' against hr_region: (images, losses, {'model': ..., 'interpolated':
+        ...}), each entry the dict of FractionsSkillScore.measure -- per channel and threshold
+        the integer tables 'num', 'den' over the ladder ``scales`` of odd neighbourhood sizes,
+        'events_pred', 'events_truth', 'used', 'fss', 'f_pred', 'f_truth', 'bias', 'target',
+        'afss' and 'skilful_scale', the smallest neighbourhood at which the image is useful --
+        plus 'thresholds' [C, T] fp32, the ones used.
+
+        thresholds: T floats (the same for every channel), a [C, T] array or a [C, T] fp32 device
+        tensor (kept by reference).  None: the truth's quantiles at ``probs``, taken on the
+        device from a srmi.distribution.DistributionScore (1024 bins) of the same two fields
+        ('q_truth', cast to fp32 on the device) -- no host read.
+
+        on="value" scores the fields themselves; on="gradient" scores the fronts: the two fields
+        are srmi.gradient.GradientScore's magnitude maps of the image and of hr_region at unit
+        spacing, whose NaN rim and coast are the mask, and the quantiles are of the truth's map.
+
+        images and losses are ``score``'s, bit for bit; the entries are views valid until the
+        next call with the same arguments.  No host synchronisation.  With graph=True the score
+        is measured after the replay, outside the captured graph.
+
+        land=True: the NaN of the image and of hr_region are the mask, pixel by pixel: what is
+        not used is "no event" in both fields ('used' is what is left)."""
+        from .distribution import DistributionScore
+        from .fss import FractionsSkillScore, check_scales
+        from .gradient import GradientScore
+        s = self.s
+        if on not in ("value", "gradient"):
+            raise ValueError(f"on {on!r}: 'value' or 'gradient'")
+        sc = check_scales(scales)
+        shape = (self.C, self.h * s, self.w * s)
+        if tuple(hr_region.shape) != shape:
+            raise ValueError(f"region shape {tuple(hr_region.shape)} != {shape}")
+        if thresholds is None:
+            pr = tuple(float(p) for p in probs)
+            if not 1 <= len(pr) <= 8:
+                raise ValueError(f"probs {probs!r}: 1 .. 8 probabilities strictly inside (0, 1)")
+            tkey = None
+        elif isinstance(thresholds, torch.Tensor):
+            pr, tkey = (), ("tensor", thresholds.data_ptr(), tuple(thresholds.shape))
+        else:
+            import numpy as np
+            pr, tkey = (), tuple(np.asarray(thresholds, dtype=np.float32).reshape(-1).tolist())
+        key = (tkey, pr, sc, on)
+        if key not in self._fss:  # before the region is inferred: the constructors refuse bad arguments
+            made = {}
+            for name in ("model", "interpolated"):
+                ds = DistributionScore(shape, 1024, 0, pr, device=self.device) if thresholds is None else None
+                thr = (torch.zeros((self.C, len(pr)), dtype=torch.float32, device=self.device) if thresholds is None
+                       else thresholds)
+                fs = FractionsSkillScore(shape, thr, sc, device=self.device)
+                gs = GradientScore(shape, (1.0, 1.0), True, device=self.device) if on == "gradient" else None
+                made[name] = (gs, ds, fs)
+            self._fss[key] = made
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        out = {}
+        for name, (gs, ds, fs) in self._fss[key].items():
+            a, b = images[name], hr
+            if gs is not None:
+                g = gs.measure(a, b)
+                a, b = g["gmag_pred"], g["gmag_truth"]
+            if ds is not None:
+                fs.thresholds.copy_(ds.measure(a, b)["q_truth"])
+            res = dict(fs.measure(a, b))
+            res["thresholds"] = fs.thresholds
             out[name] = res
         return images, losses, out
 

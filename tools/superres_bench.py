@@ -55,6 +55,16 @@ achievable HBM rate): a floor computed from shapes, not measured.  The numpy ora
 (tests/gradient_oracle.py) runs once on the host for the counts and the largest deviation of
 the map; writes profiles/gradient_bench.json.  No pass / fail bar.
 
+--fss: what does the fractions skill score cost?  ``score`` and ``score_fss`` (two C = 1 scores,
+thresholds from the truth's quantiles on the device) alternate window by window with the stage
+alone -- two srmi_fss calls on C = 2 fields, T = 4 thresholds at the truth's quantiles (0.5, 0.9,
+0.99, 0.999), scales (1, 3, 5, 9, 17, 33, 65, 129) -- with each of its three launches alone, and
+with the windows launch of a one-scale ladder at n = 3 and at n = 255, whose ratio shows that the
+cost does not follow n^2.  The bytes each launch must move (fss_launch_bytes) are reported with
+the time they take at --hbm-tbs: a floor computed from shapes, not measured.  The numpy oracle
+(tests/fss_oracle.py) runs once on the host on one channel and one threshold, where the
+device's tables must equal it; writes profiles/fss_bench.json.  No pass / fail bar.
+
 --distribution: what does the distribution score cost, and on which data?  One
 RegionSuperResolver at the last of --overlaps scores a synthetic HR truth: ``score``,
 ``score_distribution`` and, window by window in turn on one device, the score's launches alone
@@ -452,6 +462,118 @@ def gradient_main(a, spec, params, dev, kw):
            "device_map_vs_oracle_max_abs": {k: float(f"{v:.3e}") for k, v in dev_err.items()},
            "e32_map_max_abs": {k: float(f"{v:.3e}") for k, v in e32s.items()}}
     return res
+
+
+def fss_launch_bytes(C, H, W, T, N):
+    """The bytes each launch of one srmi_fss call must move (srmi.h, "the fractions skill
+    score"): events reads both fields once and writes the 2 C T bit planes and its partials;
+    windows reads the bit planes (once, if every scale shared them) and writes two int64 per
+    (channel, threshold, scale, tile); finish reads the partials it sums and writes the tables."""
+    from srmi.fss import FSS_TILE
+    px, ww = H * W, -(-W // 64)
+    planes = 2 * C * T * H * ww * 8
+    evb = -(-(H * ww) // 32)  # workgroups of the events launch per channel
+    evp = C * (1 + 2 * T) * evb * 4
+    winp = C * T * N * -(-H // FSS_TILE[0]) * ww * 16
+    return {"events": 2 * 4 * C * px + planes + evp, "windows": planes + winp,
+            "finish": C * T * 3 * evb * 4 + winp + C * T * (2 * N * 8 + 16 + (N + 6) * 8) + C * 8}
+
+
+def fss_main(a, spec, params, dev, kw):
+    import time
+
+    import numpy as np
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.distribution import DistributionScore
+    from srmi.fss import EVENTS, FINISH, WINDOWS, FractionsSkillScore
+    from srmi.superres import RegionSuperResolver
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fss_oracle as fo
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    probs, scales = (0.5, 0.9, 0.99, 0.999), (1, 3, 5, 9, 17, 33, 65, 129)
+    hr = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    rs = RegionSuperResolver(spec, params, (1, a.side, a.side), (a.tile, a.tile), (r, r), device=dev,
+                             graph=not a.no_graph, **kw)
+    for _ in range(a.warmup):
+        images, losses, _ = rs.score_fss(hr, probs=probs, scales=scales)
+    torch.cuda.synchronize()
+    # the stage alone on C = 2: (model, interpolated) against (truth, truth), and the two swapped
+    Cn, T, N = 2, len(probs), len(scales)
+    shape = (Cn, side, side)
+    pairs = [(torch.cat([images["model"], images["interpolated"]]).contiguous(), torch.cat([hr, hr]).contiguous()),
+             (torch.cat([images["interpolated"], images["model"]]).contiguous(), torch.cat([hr, hr]).contiguous())]
+    thr = DistributionScore(shape, 1024, 0, probs, device=dev).measure(*pairs[0])["q_truth"].float().contiguous()
+    scorers = [FractionsSkillScore(shape, thr, scales, device=dev) for _ in pairs]
+    small = [FractionsSkillScore(shape, thr, (3,), device=dev) for _ in pairs]
+    large = [FractionsSkillScore(shape, thr, (255,), device=dev) for _ in pairs]
+
+    def stage(objs, launches=0):
+        def fn():
+            for sc, (p, t) in zip(objs, pairs):
+                sc.measure(p, t, launches)
+        return fn
+    runs = {"score": lambda: rs.score(hr), "score_fss": lambda: rs.score_fss(hr, probs=probs, scales=scales),
+            "stage": stage(scorers), "stage_events": stage(scorers, EVENTS), "stage_windows": stage(scorers, WINDOWS),
+            "stage_finish": stage(scorers, FINISH), "windows_all_3": stage(small, WINDOWS),
+            "windows_all_255": stage(large, WINDOWS)}
+    for k, fn in runs.items():
+        if k != "score":
+            fn()  # every workspace holds a whole call's bit planes and partials before a launch runs alone
+    for fn in (stage(small), stage(large)):
+        fn()
+    torch.cuda.synchronize()
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):  # the arms alternate window by window
+        for k, fn in runs.items():
+            n = a.regions * (1 if k.startswith("score") else 4)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(n):
+                fn()
+            e1.record(st)
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / n)
+    res0 = {k: v.cpu().numpy().copy() for k, v in scorers[0].measure(*pairs[0]).items()}
+    torch.cuda.synchronize()
+    p0, t0 = pairs[0][0][:1].cpu().numpy(), pairs[0][1][:1].cpu().numpy()
+    thr0 = thr[:1, 1:2].cpu().numpy()
+    tic = time.perf_counter()
+    o = fo.fss(p0, t0, thr0, scales)  # one channel and one threshold of the 2 x 4: an eighth of one measure
+    host = time.perf_counter() - tic
+    if not (np.array_equal(o["num"][0, 0], res0["num"][0, 1]) and np.array_equal(o["den"][0, 0], res0["den"][0, 1])
+            and o["used"][0] == res0["used"][0]):
+        raise SystemExit("superres_bench: the tables differ from the oracle's")
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    per_call = fss_launch_bytes(Cn, side, side, T, N)
+    nbytes = {"stage_" + k: 2 * v for k, v in per_call.items()}  # two measures per stage call
+    nbytes["stage"] = sum(nbytes.values())
+    return {"tool": "superres_bench --fss", "device": torch.cuda.get_device_name(0),
+            "config": {"workload": f"rcan-10-20-64 score_fss, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR tile {a.tile}, "
+                                   f"overlap {r}: two C = 1 scores (model, interpolated) per score_fss call, thresholds "
+                                   "from the truth's quantiles on the device; the stage arms: two srmi_fss calls on C = 2 "
+                                   f"fields [2, {side}, {side}] ((model, interpolated) and the two swapped, against the "
+                                   "truth twice)",
+                       "probs": list(probs), "scales": list(scales), "T": T, "N": N,
+                       "network": "untrained (seeded initial weights, synthetic fields)",
+                       "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                       "regions_per_window": a.regions, "stage_calls_per_window": a.regions * 4,
+                       "workspace_mib_per_score": round(scorers[0].workspace.numel() / 2 ** 20, 2), "hbm_tbs": a.hbm_tbs},
+            "ms": {k: {"median": round(med[k], 4), "min_max": [round(min(v), 4), round(max(v), 4)]} for k, v in ms.items()},
+            "score_fss_over_score": round(med["score_fss"] / med["score"], 4),
+            "stage_over_score": round(med["stage"] / med["score"], 5),
+            "launch_bytes": {k: int(v) for k, v in nbytes.items()},
+            "launch_memory_floor_ms": {k: round(v / (a.hbm_tbs * 1e12) * 1e3, 5) for k, v in nbytes.items()},
+            "launch_time_over_floor": {k: round(med[k] / (v / (a.hbm_tbs * 1e12) * 1e3), 2) for k, v in nbytes.items()},
+            "windows_all_255_over_all_3": round(med["windows_all_255"] / med["windows_all_3"], 3),
+            "n_squared_ratio_255_over_3": round((255 / 3) ** 2, 1),
+            "fss_model": [round(float(v), 5) for v in res0["fss"][0, 1]],
+            "fss_interpolated": [round(float(v), 5) for v in res0["fss"][1, 1]],
+            "skilful_scale": res0["skilful_scale"].tolist(), "used": res0["used"].tolist(),
+            "host_oracle_s_one_channel_one_threshold": round(host, 2),
+            "host_oracle_s_two_measures_extrapolated": round(host * Cn * T * 2, 1),
+            "tables_equal_the_oracle_on_that_slice": True}
 
 
 def distribution_main(a, spec, params, dev, kw):
@@ -862,6 +984,7 @@ def main():
                     help="time score_spectra's spectral stage at this window (default 256) beside score")
     ap.add_argument("--ssim", action="store_true", help="time score_ssim's SSIM stage beside score")
     ap.add_argument("--gradient", action="store_true", help="time score_gradient's stage beside score")
+    ap.add_argument("--fss", action="store_true", help="time score_fss, its stage and each of its launches beside score")
     ap.add_argument("--hbm-tbs", type=float, default=6.3, help="achievable HBM rate the memory floor is taken at")
     ap.add_argument("--distribution", action="store_true",
                     help="time score_distribution's stage beside score and the SSIM stage, on a smooth and a white input")
@@ -873,13 +996,14 @@ def main():
                     help="time the quantile map's launches and the region with the map on and off, and score both")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
                                                 "spectra_bench.json, ssim_bench.json, gradient_bench.json, "
+                                                "fss_bench.json, "
                                                 "distribution_bench.json, "
                                                 "ensemble_bench.json, consistency_bench.json, "
                                                 "quantile_map_bench.json)")
     a = ap.parse_args()
     if (sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution
-            + a.quantile_map + a.gradient > 1):
-        raise SystemExit("superres_bench: --land, --spectra, --ssim, --gradient, --distribution, --ensemble, "
+            + a.quantile_map + a.gradient + a.fss > 1):
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --gradient, --fss, --distribution, --ensemble, "
                          "--consistent and --quantile-map are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
@@ -888,6 +1012,7 @@ def main():
                              "spectra_bench.json" if a.spectra is not None else
                              "ssim_bench.json" if a.ssim else
                              "gradient_bench.json" if a.gradient else
+                             "fss_bench.json" if a.fss else
                              "distribution_bench.json" if a.distribution else
                              "ensemble_bench.json" if a.ensemble is not None else
                              "consistency_bench.json" if a.consistent is not None else
@@ -908,11 +1033,12 @@ def main():
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
     if (a.land is not None or a.spectra is not None or a.ssim or a.distribution or a.ensemble is not None
-            or a.consistent is not None or a.quantile_map or a.gradient):
+            or a.consistent is not None or a.quantile_map or a.gradient or a.fss):
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
                           ssim_main(a, spec, params, dev, kw) if a.ssim else
                           gradient_main(a, spec, params, dev, kw) if a.gradient else
+                          fss_main(a, spec, params, dev, kw) if a.fss else
                           distribution_main(a, spec, params, dev, kw) if a.distribution else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
                           quantile_map_main(a, spec, params, dev, kw) if a.quantile_map else
