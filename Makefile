@@ -6,7 +6,7 @@ SRC := $(PKG)/csrc
 OUT := $(PKG)/srmi/libsrmi.so
 OBJDIR ?= build/obj
 CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function -Iinclude $(EXTRA)
-HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip $(SRC)/gradient.hip $(SRC)/gradient_loss.hip $(SRC)/fss.hip
+HIPSRC := $(SRC)/conv3x3.hip $(SRC)/conv_f32.hip $(SRC)/wgrad3x3.hip $(SRC)/small.hip $(SRC)/tiles.hip $(SRC)/rcab_infer.hip $(SRC)/spectra.hip $(SRC)/spectral_loss.hip $(SRC)/consistency.hip $(SRC)/ssim.hip $(SRC)/ssim_loss.hip $(SRC)/distribution.hip $(SRC)/quantile_map.hip $(SRC)/gradient.hip $(SRC)/gradient_loss.hip $(SRC)/fss.hip $(SRC)/ensemble_score.hip
 CPPSRC := $(SRC)/engine.cpp
 OBJS := $(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIPSRC)) $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(CPPSRC))
 HDRS := $(wildcard $(SRC)/*.hpp) include/srmi.h
@@ -15,6 +15,12 @@ HDRS := $(wildcard $(SRC)/*.hpp) include/srmi.h
 # roots and quotients must be the correctly rounded ones, whatever the compiler's default is
 GRADOBJS := $(OBJDIR)/gradient.o $(OBJDIR)/gradient_loss.o build/obj_stamps/gradient.o build/obj_stamps/gradient_loss.o
 $(GRADOBJS): CXXFLAGS += -fhip-fp32-correctly-rounded-divide-sqrt
+
+# the ensemble score states its fp64 arithmetic operation by operation (srmi.h).  The __d*_rn
+# forms are plain operators to this compiler, which fuses a product into a following sum under
+# the default contraction setting: the file is built with contraction off
+ENSOBJS := $(OBJDIR)/ensemble_score.o build/obj_stamps/ensemble_score.o
+$(ENSOBJS): CXXFLAGS += -ffp-contract=off
 
 all: $(OUT)
 

@@ -119,6 +119,12 @@
  *                                   and of a truth in n x n neighbourhoods, for a ladder of n,
  *                                   and the skilful scale.  No reference counterpart: the
  *                                   reference scores a field by its RMSE alone.
+ *   srmi_ensemble_score_workspace,
+ *   srmi_ensemble_score          -> an ensemble of K fields against a truth: CRPS (plain and
+ *                                   fair), the rank histogram, the spread-skill ratio with a
+ *                                   spread-binned reliability table, the spread-|error|
+ *                                   correlation and a per-pixel CRPS map.  No reference
+ *                                   counterpart: the reference has no ensemble.
  */
 #ifndef SRMI_H
 #define SRMI_H
@@ -896,6 +902,76 @@ int srmi_fss_workspace(int C, int H, int W, int T, int N, size_t* bytes);
 int srmi_fss(const float* pred, const float* truth, int C, int H, int W, const float* thresholds, int T,
              const int* scales, int N, void* workspace, size_t workspace_bytes, long long* num, long long* den,
              long long* events, long long* used, double* derived, int launches, void* stream);
+
+/* ---- the ensemble score (no reference counterpart) ---------------------- */
+/* Does an ensemble's spread say where to trust its mean?  K fields against a truth: the CRPS of
+ * the empirical distribution (plain and fair, Ferro 2014), the rank (Talagrand) histogram, the
+ * spread-skill ratio (Fortin et al. 2014) with a reliability table binned by the spread, the
+ * Pearson correlation of spread and |error|, and a per-pixel CRPS map;
+ * tests/ensemble_score_oracle.py restates it in numpy.  The K = 1 case of
+ * srmi_tiles_blend_ensemble (one slab, its single-bit mask, spread == NULL) returns B_j bit for
+ * bit (mean = B_j / 1.0f), which is how the members of a self-ensemble are materialised.
+ *   Inputs: members [K][C][H][W] fp32, 2 <= K <= 8, and truth [C][H][W] fp32 on the device, NaN /
+ *   Inf allowed; edges [C][B - 1] fp32 ON THE DEVICE (so that a device-side quantile can fill
+ *   them without a host read): the interior edges of B spread bins, 1 <= B <= 16; with B == 1 the
+ *   pointer is not read and may be NULL.
+ *   Per channel c.  Used pixel: the truth and all K members are finite there.  Per used pixel,
+ *   with m_j the members and y the truth converted to fp64 (exact), every operation below one
+ *   IEEE fp64 operation rounded to nearest, never fused, so numpy's float64 elementwise
+ *   operations give the same bits; tree(t) = ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7))
+ *   with the terms j >= K left out, as srmi_tiles_blend_ensemble adds:
+ *     a     = tree(|m_j - y|)
+ *     b     = the running sum, from 0, of |m_j - m_l| over j < l in lexicographic (j, l)
+ *     crps  = a / K - b / (K K)                 crps_fair = a / K - b / (K (K - 1))
+ *     mean  = tree(m_j) / K                     var = tree((m_j - mean) (m_j - mean)) / K
+ *     e     = mean - y                          s   = sqrt(var)
+ *     rank  = the number of j with m_j < y and tied = any m_j == y, by fp32 comparisons
+ *     bin   = the number of i < B - 1 with (float)s >= edges[c][i]   (a NaN edge never counts;
+ *             edges that ascend make this the bin of s, but nothing requires them to)
+ *   counts [C][K + 3 + B] int64 = {used, rank_hist[K + 1], tied, bin_count[B]}: exact.
+ *   sums [C][9 + 2 B] fp64 = the sums over the used pixels of {crps, crps_fair, a, b, var, e e,
+ *   |e|, s, s |e|}, then per bin {var, e e}.  The order of the additions is fixed (a lane's
+ *   pixels ascending, a fixed tree over the lanes of a workgroup, then in the finish launch a
+ *   lane's workgroups ascending and a fixed tree over the lanes of a wave): the same bits on every run.  All terms
+ *   are >= 0, so a sum of T terms is within T 2^-53 of the exact one, relatively.
+ *   derived [C][9 + 2 B] fp64, written by one thread of the finish launch from counts and sums
+ *   alone, each operation rounded once, in this order: n = (double)used, f = (double)(K + 1) /
+ *   (double)(K - 1), mse = S_ee / n, mvar = S_var / n, rmse = sqrt(mse); then
+ *     [0] crps = S_crps / n                     [1] crps_fair = S_fair / n
+ *     [2] rmse_mean = rmse                      [3] spread_rms = sqrt(mvar)
+ *     [4] ssr = sqrt(f mvar) / rmse     (Fortin et al. 2014 with the ddof-1 variance: 1 when the
+ *         truth is exchangeable with the members)
+ *     [5] spread_error_corr = cov / sqrt(vs va) with ms = S_s / n, ma = S_|e| / n, cov = S_s|e| / n
+ *         - ms ma, vs = mvar - ms ms, va = mse - ma ma  (the IEEE result: NaN for 0 / 0 or a
+ *         negative product)
+ *     [6] outliers = (double)(h_0 + h_K) / n    [7] its expectation 2.0 / (double)(K + 1)
+ *     [8] reliability_index = the running sum, from 0 in ascending r, of |(double)h_r / n - u|, u =
+ *         1.0 / (double)(K + 1)
+ *     [9 + b] bin_spread = sqrt(f (S_var,b / n_b))     [9 + B + b] bin_rmse = sqrt(S_ee,b / n_b)
+ *         (an empty bin: NaN in both)
+ *   A channel without a used pixel has NaN in every derived entry and 0 in every table and sum.
+ *   crps_map [C][H][W] fp32 (optional, NULL: not written) = (float)crps, the canonical NaN
+ *   0x7fc00000 where the pixel is not used.
+ * Two launches on `stream`: main (one read of the K + 1 fields, (K + 1) C H W 4 bytes, plus C H W 4
+ * with the map; a workgroup owns 4096 consecutive pixels of a plane and a lane four consecutive
+ * ones per step, loaded and stored as 16 bytes where the channel's K + 1 (+ 1) planes all start
+ * on 16-byte boundaries, one by one otherwise and in a ragged last quad -- the same values and
+ * order either way) and finish.  No global atomics, no host synchronisation, no allocation:
+ * capturable.  srmi_ensemble_score_workspace (host only) gives the bytes of `workspace` (16-byte
+ * aligned; it need not be initialised): per channel and workgroup of the main launch, ceil(H W /
+ * 4096) of them, 9 + 2 B doubles and K + 3 + B uint32.  members, truth, edges and crps_map have no
+ * alignment requirement.  K, B, C, H or W out of range, a missing members, truth, edges (B > 1),
+ * workspace, counts, sums or derived, a workspace that is too small or misaligned, unknown
+ * `launches` bits: SRMI_ERR_ARG; H W > 2^31 - 1: SRMI_ERR_SHAPE; nothing launched and no output
+ * touched.  launches: 0 for both, or SRMI_ENSEMBLE_SCORE_* bits for one alone (for timing a launch
+ * by itself: finish reads what the main launch of a previous call left in the workspace).
+ * K > 8, randomised tie-breaking of ranks and a loss term are out of scope. */
+#define SRMI_ENSEMBLE_SCORE_MAIN 1
+#define SRMI_ENSEMBLE_SCORE_FINISH 2
+int srmi_ensemble_score_workspace(int K, int C, int H, int W, int B, size_t* bytes);
+int srmi_ensemble_score(const float* members, const float* truth, int K, int C, int H, int W, const float* edges,
+                        int B, void* workspace, size_t workspace_bytes, long long* counts, double* sums,
+                        double* derived, float* crps_map, int launches, void* stream);
 
 /* ---- quantile mapping (no reference counterpart) ------------------------- */
 /* Empirical quantile mapping: a monotone transfer function T = F_truth^-1 o F_src, calibrated

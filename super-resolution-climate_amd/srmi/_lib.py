@@ -193,6 +193,9 @@ _SIGS = {
     "srmi_fss_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
     "srmi_fss": ([P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.POINTER(C.c_int), C.c_int, P, C.c_size_t, P, P, P, P, P,
                   C.c_int, P], C.c_int),
+    "srmi_ensemble_score_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)], C.c_int),
+    "srmi_ensemble_score": ([P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, P, C.c_size_t, P, P, P, P, C.c_int,
+                             P], C.c_int),
 }
 EXPORTED = tuple(_SIGS)
 

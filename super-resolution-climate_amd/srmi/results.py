@@ -488,6 +488,105 @@ def load_fss(path: str) -> Tuple[Dict[str, np.ndarray], List[str], np.ndarray, T
         return out, names.split(",") if names else [], thr, sc
 
 
+ENSEMBLE_TABLES = ("used", "rank_hist", "tied", "bin_count")
+ENSEMBLE_SCALARS = ("crps", "crps_fair", "rmse_mean", "spread_rms", "ssr", "spread_error_corr", "outliers",
+                    "outliers_expected", "reliability_index")  # srmi.ensemble_score.ENS_DERIVED
+ENSEMBLE_BINS = ("bin_spread", "bin_rmse")
+
+
+def save_ensemble_score(path: str, score: Dict[str, object], varnames: Sequence[str]) -> str:
+    """One ensemble score (the dict of srmi.ensemble_score.EnsembleScore.measure, e.g.
+    RegionSuperResolver.score_ensemble's third result) as a netCDF-3 file, through the same scipy
+    writer.  The integer tables -- 'used', 'tied' on ('channel',), 'rank_hist' on ('channel',
+    'rank'), 'bin_count' on ('channel', 'bin') -- are written as PAIRS of int32, '<name>_hi' and
+    '<name>_lo' (value = hi 2^32 + lo as unsigned), as save_fss writes its tables; 'sums' is
+    float64 on ('channel', 'sum'), the derived values float64 on ('channel',) and 'bin_spread',
+    'bin_rmse' on ('channel', 'bin'), all with ``_FillValue = NaN``; 'edges' float32 on
+    ('channel', 'edge') (left out with one bin: netCDF-3 has no empty dimension); 'crps_map',
+    when the score holds one, float32 on ('channel', 'y', 'x'); the attribute ``varnames`` holds
+    the channel names joined by ``,``.  K is the length of 'rank' minus one.  No reference
+    counterpart."""
+    from scipy.io import netcdf_file
+    keys = ENSEMBLE_TABLES + ENSEMBLE_SCALARS + ENSEMBLE_BINS + ("sums", "edges")
+    missing = [k for k in keys if k not in score]
+    if missing:
+        raise ValueError(f"score lacks {missing}")
+    n = len(varnames)
+    hist = _np(score["rank_hist"])
+    bins = _np(score["bin_count"])
+    if hist.ndim != 2 or bins.ndim != 2:
+        raise ValueError(f"rank_hist {hist.shape} and bin_count {bins.shape}: [C, K + 1] and [C, B] are needed")
+    B = bins.shape[1]
+    sizes = {"channel": n, "rank": hist.shape[1], "bin": B, "sum": 9 + 2 * B}
+    if B > 1:
+        sizes["edge"] = B - 1
+    dims = {"used": ("channel",), "tied": ("channel",), "rank_hist": ("channel", "rank"),
+            "bin_count": ("channel", "bin"), "sums": ("channel", "sum"), "edges": ("channel", "edge")}
+    dims.update({q: ("channel",) for q in ENSEMBLE_SCALARS})
+    dims.update({q: ("channel", "bin") for q in ENSEMBLE_BINS})
+    arrays = {}
+    for q in keys:
+        a = _np(score[q])
+        a = np.ascontiguousarray(a.astype(np.int64 if q in ENSEMBLE_TABLES else np.float32 if q == "edges"
+                                          else np.float64))
+        shape = tuple(sizes.get(d, 0) for d in dims[q])
+        if a.shape != shape:
+            raise ValueError(f"{q}: {a.shape} is not {shape}")
+        arrays[q] = a
+    cmap = None
+    if score.get("crps_map") is not None:
+        cmap = np.ascontiguousarray(_np(score["crps_map"]).astype(np.float32))
+        if cmap.ndim != 3 or cmap.shape[0] != n:
+            raise ValueError(f"crps_map: {cmap.shape} is not [{n}, H, W]")
+        sizes["y"], sizes["x"] = cmap.shape[1], cmap.shape[2]
+    if os.path.exists(path):
+        os.remove(path)
+    with netcdf_file(path, "w", version=2) as f:
+        f.varnames = ",".join(str(v) for v in varnames)
+        for d, size in sizes.items():
+            f.createDimension(d, size)
+        for q in ENSEMBLE_TABLES:
+            u = arrays[q].view(np.uint64)
+            for part, half in (("hi", u >> np.uint64(32)), ("lo", u & np.uint64(0xFFFFFFFF))):
+                dv = f.createVariable(f"{q}_{part}", np.int32, dims[q])
+                dv[:] = half.astype(np.uint32).view(np.int32)
+        for q in ENSEMBLE_SCALARS + ENSEMBLE_BINS + ("sums",):
+            dv = f.createVariable(q, np.float64, dims[q])
+            dv._FillValue = np.array([np.nan], dtype=np.float64)
+            dv[:] = arrays[q]
+        if B > 1:
+            ev = f.createVariable("edges", np.float32, dims["edges"])
+            ev._FillValue = np.array([np.nan], dtype=np.float32)
+            ev[:] = arrays["edges"]
+        if cmap is not None:
+            mv = f.createVariable("crps_map", np.float32, ("channel", "y", "x"))
+            mv._FillValue = np.array([np.nan], dtype=np.float32)
+            mv[:] = cmap
+    return path
+
+
+def load_ensemble_score(path: str) -> Tuple[Dict[str, np.ndarray], List[str]]:
+    """The inverse of save_ensemble_score: (the score as numpy arrays, the tables int64 again,
+    'edges' [C, B - 1] fp32, 'crps_map' when the file holds one; varnames)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(path, "r", mmap=False) as f:
+        names = f.varnames.decode() if isinstance(f.varnames, bytes) else str(f.varnames)
+        out = {}
+        for q in ENSEMBLE_TABLES:
+            hi = np.array(f.variables[f"{q}_hi"][:], dtype=np.int32).view(np.uint32).astype(np.uint64)
+            lo = np.array(f.variables[f"{q}_lo"][:], dtype=np.int32).view(np.uint32).astype(np.uint64)
+            out[q] = ((hi << np.uint64(32)) | lo).view(np.int64)
+        for q in ENSEMBLE_SCALARS + ENSEMBLE_BINS + ("sums",):
+            out[q] = np.array(f.variables[q][:], dtype=np.float64)
+        if "edges" in f.variables:
+            out["edges"] = np.array(f.variables["edges"][:], dtype=np.float32)
+        else:
+            out["edges"] = np.zeros((out["used"].shape[0], 0), dtype=np.float32)
+        if "crps_map" in f.variables:
+            out["crps_map"] = np.array(f.variables["crps_map"][:], dtype=np.float32)
+        return out, names.split(",") if names else []
+
+
 DISTRIBUTION_SCALARS = ("pss", "w1", "under", "over")
 DISTRIBUTION_QUANTILES = ("q_pred", "q_truth", "q_bias")
 DISTRIBUTION_TABLES = ("hist_pred", "hist_truth")

@@ -72,6 +72,19 @@ the spread the cheapest honest proxy for where to trust the field.  With ``land=
 variants are transforms of the FILLED tile, and both images are re-masked.  The cost is
 K forwards; the two added launches are noise beside them.
 
+Members (``members=True``, with ``ensemble`` > 1)
+-------------------------------------------------
+The K blended, back-transformed member fields as a product, 'members' [K, C, s h, s w]: member j
+is the blend of variant ``variants[j]`` alone, de-normalised -- the B_j whose mean and standard
+deviation 'model' and 'spread' are.  No kernel of its own: ``srmi_tiles_blend_ensemble`` called on
+slab j with the single-bit mask ``1 << variants[j]`` and no spread returns B_j bit for bit (the K
+= 1 case of its contract), so K such calls behind the blend, inside the captured graph, write
+them (``land=True``: re-masked as 'model' is).  The members are the RAW blended outputs: they
+come BEFORE ``quantile_map`` and BEFORE ``consistent=K``, which change 'model' and leave
+'members' and 'spread' as they are; with neither, the pairwise fp32 mean and spread of
+'members' are 'model' and 'spread' bit for bit.  ``score_ensemble`` verifies them against a truth
+(srmi.ensemble_score: CRPS, rank histogram, spread-skill ratio, reliability table).
+
 Consistency (``consistent=K``, 1 <= K <= 16)
 --------------------------------------------
 Nothing above ties D('model') to the input, D being the task's downsample: the tiles are
@@ -214,7 +227,7 @@ class RegionSuperResolver:
                  tile_lr: Tuple[int, int] = (48, 48), overlap: Tuple[int, int] = (8, 8), norm: Optional[str] = None,
                  task=None, stats=None, micro: Optional[int] = None, max_batch: int = 512, graph: bool = False,
                  device: Optional[torch.device] = None, land: bool = False, min_wet: float = 0.25, ensemble=1,
-                 consistent: int = 0, quantile_map=None, qm_strength: float = 1.0):
+                 consistent: int = 0, quantile_map=None, qm_strength: float = 1.0, members: bool = False):
         """region_chw_lr: (C, h, w) of the LR regions; tile_lr: the LR tile the engine
         runs; overlap: LR pixels per axis, 0 <= overlap <= tile // 2 (stride = tile -
         overlap).
@@ -271,7 +284,12 @@ class RegionSuperResolver:
         the next replay, with no recapture -- as long as the map's ``on`` stays what it was,
         because whether the base is passed is part of the captured launch; qm_strength and
         ``on`` are fixed at construction (a state of another ``on`` needs a new resolver).
-        quantile_map=None is the object as it was, bit for bit."""
+        quantile_map=None is the object as it was, bit for bit.
+
+        members: with ensemble > 1 (ValueError otherwise), the images gain 'members' [K, C, s h,
+        s w], the K blended member fields before ``quantile_map`` and ``consistent`` (see the
+        module docstring), at K more blend launches and K output-sized planes.  members=False is
+        the object as it was, bit for bit: no buffer, image key or launch is added."""
         if task is None:  # the active srmi ConfigContext's task section, if any
             from . import config as _config
             task = _config._CURRENT.get("task") if _config._CURRENT is not None else None
@@ -314,6 +332,9 @@ class RegionSuperResolver:
         self.variants = ensemble_variants(ensemble, (ty, tx))
         self.vmask = sum(1 << f for f in self.variants)
         K = self.K = len(self.variants)
+        self.members = bool(members)
+        if self.members and K == 1:
+            raise ValueError("members=True needs ensemble > 1: one variant has no members beside 'model'")
         s = spec.scale
         self.C, self.h, self.w, self.ty, self.tx, self.s = C, h, w, ty, tx, s
         self.land = bool(land)
@@ -350,6 +371,8 @@ class RegionSuperResolver:
                        "model": torch.empty((C, h * s, w * s), **f32)}
         if K > 1:
             self.images["spread"] = torch.empty((C, h * s, w * s), **f32)
+        if self.members:
+            self.images["members"] = torch.empty((K, C, h * s, w * s), **f32)
         if self.land:
             self.nwet = torch.zeros((n, C), dtype=torch.int32, device=d)
             self.up = torch.empty((n, C, ty * s, tx * s), **f32)  # the tiled baseline's tiles
@@ -386,6 +409,7 @@ class RegionSuperResolver:
         self._distribution = {}  # (bins, joint, probs, value_range) -> the DistributionScore of each image
         self._gradient = {}  # (spacing, maps, distribution) -> (GradientScore, DistributionScore | None) of each image
         self._fss = {}  # (thresholds, probs, scales, on) -> the scorers of each image (score_fss)
+        self._ens = {}  # (edges, probs, crps_map) -> (DistributionScore | None, EnsembleScore) (score_ensemble)
         self._use_graph = bool(graph) and self.device.type == "cuda"
 
     # ---------------------------------------------------------------- pieces
@@ -444,6 +468,14 @@ class RegionSuperResolver:
         call("srmi_tiles_blend", ptr(self.sr), ptr(self.off), ptr(self.div), ptr(self.bad), self.C, self.ty * s,
              self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s, ptr(self.images["model"]), stream_handle())
 
+    def _members(self):
+        """'members'[j] <- the blend of slab j alone: the ensemble blend's K = 1 case, B_j bit for bit."""
+        s = self.s
+        for j, f in enumerate(self.variants):
+            call("srmi_tiles_blend_ensemble", ptr(self.sr[j]), 1 << f, ptr(self.off), ptr(self.div), ptr(self.bad),
+                 self.C, self.ty * s, self.tx * s, self.sy * s, self.sx * s, self.h * s, self.w * s,
+                 ptr(self.region) if self.land else None, s, ptr(self.images["members"][j]), None, stream_handle())
+
     def _run(self, use_map: bool = True, correct: bool = True):
         self._cut()
         if self.K > 1:
@@ -455,6 +487,8 @@ class RegionSuperResolver:
         else:
             upsample(self.region[None], self.s, out=self.images["interpolated"][None], mode=self.umode)
         self._blend()
+        if self.members:
+            self._members()
         if use_map and self.quantile_map is not None:
             qm, model = self.quantile_map, self.images["model"]
             if qm.on != self._qm_on:
@@ -509,7 +543,11 @@ class RegionSuperResolver:
         consistent > 0: 'model' is the corrected field (the module docstring), 'residual'
         [C, h, w] the input minus the downsample of the uncorrected one and
         'residual_left' [C, h, w] what the corrected one still misses, both 0 at the LR
-        cells that take no part; 'interpolated' and 'spread' are what they are without."""
+        cells that take no part; 'interpolated' and 'spread' are what they are without.
+
+        members=True: 'members' [K, C, s h, s w], member j the blended, de-normalised output of
+        variant ``variants[j]`` alone, NaN where 'model' is -- the raw blended outputs, before
+        the quantile map and the consistency correction."""
         if tuple(lr_region.shape) != (self.C, self.h, self.w):
             raise ValueError(f"region shape {tuple(lr_region.shape)} != {(self.C, self.h, self.w)}")
         self.region.copy_(lr_region)
@@ -759,6 +797,63 @@ class RegionSuperResolver:
             res["thresholds"] = fs.thresholds
             out[name] = res
         return images, losses, out
+
+    def score_ensemble(self, hr_region: torch.Tensor, edges=None,
+                       probs=(0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9), crps_map: bool = False):
+        """``score``, then the ensemble score (srmi.ensemble_score.EnsembleScore) of 'members'
+        against hr_region: (images, losses, result), result the dict of EnsembleScore.measure --
+        per channel the exact tables 'used', 'rank_hist', 'tied', 'bin_count', the fp64 'sums',
+        and 'crps', 'crps_fair', 'rmse_mean', 'spread_rms', 'ssr', 'spread_error_corr',
+        'outliers', 'outliers_expected', 'reliability_index', the reliability table 'bin_spread'
+        / 'bin_rmse' over the spread bins, 'edges' [C, B - 1] fp32, the ones used, and with
+        crps_map=True 'crps_map' [C, s h, s w].  It needs members=True: ValueError otherwise.
+
+        edges: the interior edges of the spread bins -- B - 1 floats (the same for every
+        channel), a [C, B - 1] array or a [C, B - 1] fp32 device tensor (kept by reference).
+        None: the quantiles of 'spread' at ``probs`` (1 .. 15 probabilities), taken on the device
+        from a srmi.distribution.DistributionScore (1024 bins) of 'spread' and cast to fp32 on
+        the device -- no host read -- so that the bins hold about equal numbers of pixels.
+
+        What is scored are the members, the raw blended outputs: on a resolver with a
+        quantile_map or consistent=K the rmse_mean here is that of the members' own mean, not of
+        the mapped or corrected 'model' (scoring those is out of scope).
+
+        images and losses are ``score``'s, bit for bit; the entries are views valid until the
+        next call with the same arguments.  No host synchronisation.  With graph=True the score
+        is measured after the replay, outside the captured graph.
+
+        land=True: the NaN of the members and of hr_region are the mask, pixel by pixel ('used'
+        is what is left)."""
+        from .distribution import DistributionScore
+        from .ensemble_score import MAX_BINS, EnsembleScore
+        if not self.members:
+            raise ValueError("score_ensemble needs the member fields: build the resolver with members=True (and "
+                             "ensemble > 1)")
+        s = self.s
+        shape = (self.C, self.h * s, self.w * s)
+        if tuple(hr_region.shape) != shape:
+            raise ValueError(f"region shape {tuple(hr_region.shape)} != {shape}")
+        if edges is None:
+            pr = tuple(float(p) for p in probs)
+            if not 1 <= len(pr) <= MAX_BINS - 1:
+                raise ValueError(f"probs {probs!r}: 1 .. {MAX_BINS - 1} probabilities strictly inside (0, 1)")
+            ekey = None
+        elif isinstance(edges, torch.Tensor):
+            pr, ekey = (), ("tensor", edges.data_ptr(), tuple(edges.shape))
+        else:
+            import numpy as np
+            pr, ekey = (), tuple(np.asarray(edges, dtype=np.float32).reshape(-1).tolist())
+        key = (ekey, pr, bool(crps_map))
+        if key not in self._ens:  # before the region is inferred: the constructors refuse bad arguments
+            ds = DistributionScore(shape, 1024, 0, pr, device=self.device) if edges is None else None
+            ed = torch.zeros((self.C, len(pr)), dtype=torch.float32, device=self.device) if edges is None else edges
+            self._ens[key] = (ds, EnsembleScore((self.K,) + shape, ed, bool(crps_map), device=self.device))
+        images, losses = self.score(hr_region)
+        hr = hr_region.contiguous()
+        ds, es = self._ens[key]
+        if ds is not None:
+            es.edges.copy_(ds.measure(images["spread"], images["spread"])["q_truth"])
+        return images, losses, es.measure(images["members"], hr)
 
     def fit_quantile_map(self, hr_regions, bins: int = 256, on: str = "detail", value_range=None,
                          tail_count: int = 16):

@@ -65,6 +65,18 @@ the time they take at --hbm-tbs: a floor computed from shapes, not measured.  Th
 (tests/fss_oracle.py) runs once on the host on one channel and one threshold, where the
 device's tables must equal it; writes profiles/fss_bench.json.  No pass / fail bar.
 
+--ensemble-score: what do the member fields and the ensemble score cost?  For K = 4 and 8, two
+RegionSuperResolver(ensemble=K), members=True and members=False, on the default region at the
+last of --overlaps.  The arms alternate window by window on one device: the region with members
+off and on, ``score`` and ``score_ensemble`` (edges from the spread's quantiles on the device),
+the K member launches alone, and the score's stage alone -- one srmi_ensemble_score call on the
+[K, 1, 4096, 4096] members (B = 10), its main launch alone without and with the CRPS map, and its
+finish launch alone.  The bytes the main launch must move, (K + 1) H W 4 (+ H W 4 with the map),
+are reported with the time they take at --hbm-tbs: a floor computed from shapes, not measured.
+Also reports what the score says of this ensemble; writes profiles/ensemble_score_bench.json.
+No pass / fail bar.  The weights are default_init_'s, untrained: the numbers say nothing about
+the calibration of a trained network on real data.
+
 --distribution: what does the distribution score cost, and on which data?  One
 RegionSuperResolver at the last of --overlaps scores a synthetic HR truth: ``score``,
 ``score_distribution`` and, window by window in turn on one device, the score's launches alone
@@ -901,6 +913,84 @@ def ensemble_main(a, spec, params, lr, dev, kw):
     return res
 
 
+def ensemble_score_main(a, spec, params, lr, dev, kw):
+    from oracle.rcan_oracle import synthetic_hr
+    from srmi.ensemble_score import FINISH, MAIN, EnsembleScore
+    from srmi.superres import RegionSuperResolver
+    r, s = a.overlaps[-1], spec.scale
+    side = a.side * s
+    px = side * side
+    hr = torch.tensor(synthetic_hr(1, 1, side, 98)[0]).to(dev)
+    st = torch.cuda.current_stream()
+    res = {"tool": "superres_bench --ensemble-score", "device": torch.cuda.get_device_name(0),
+           "config": {"workload": f"rcan-10-20-64, 1 var, {a.side}^2 LR region -> {side}^2 HR, LR tile {a.tile}, overlap "
+                                  f"{r}; the stage arms: one srmi_ensemble_score call on members [K, 1, {side}, {side}], "
+                                  "B = 10 spread bins at the spread's deciles",
+                      "network": "untrained (default_init_, synthetic fields): no claim about calibration on real data",
+                      "graph": not a.no_graph, "warmup": a.warmup, "repeats": a.repeats,
+                      "regions_per_window": a.regions, "stage_calls_per_window": a.regions * 4, "hbm_tbs": a.hbm_tbs},
+           "K": {}}
+    for K in (4, 8):
+        mk = dict(device=dev, graph=not a.no_graph, ensemble=K, **kw)
+        on = RegionSuperResolver(spec, params, tuple(lr.shape), (a.tile, a.tile), (r, r), members=True, **mk)
+        off = RegionSuperResolver(spec, params, tuple(lr.shape), (a.tile, a.tile), (r, r), **mk)
+        for _ in range(a.warmup):
+            off.super_resolve(lr)
+            on.super_resolve(lr)
+            images, losses, got = on.score_ensemble(hr)
+        torch.cuda.synchronize()
+        members = images["members"]
+        edges = got["edges"].clone()
+        plain = EnsembleScore((K, 1, side, side), edges, False, device=dev)
+        mapped = EnsembleScore((K, 1, side, side), edges, True, device=dev)
+        runs = {"region_members_off": lambda: off.super_resolve(lr), "region_members_on": lambda: on.super_resolve(lr),
+                "score": lambda: on.score(hr), "score_ensemble": lambda: on.score_ensemble(hr),
+                "member_launches": on._members, "stage": lambda: plain.measure(members, hr),
+                "stage_main": lambda: plain.measure(members, hr, MAIN),
+                "stage_main_with_map": lambda: mapped.measure(members, hr, MAIN),
+                "stage_finish": lambda: plain.measure(members, hr, FINISH)}
+        for fn in runs.values():
+            fn()  # every workspace holds a whole call's partials before a launch runs alone
+        torch.cuda.synchronize()
+        ms = {k: [] for k in runs}
+        for _ in range(a.repeats):  # the arms alternate window by window
+            for k, fn in runs.items():
+                n = a.regions * (1 if k.startswith(("region", "score")) else 4)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(n):
+                    fn()
+                e1.record(st)
+                e1.synchronize()
+                ms[k].append(e0.elapsed_time(e1) / n)
+        images, losses, got = on.score_ensemble(hr)
+        torch.cuda.synchronize()
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        nbytes = {"stage_main": (K + 1) * px * 4, "stage_main_with_map": (K + 2) * px * 4}
+        ratios = [x / y for x, y in zip(ms["region_members_on"], ms["region_members_off"])]
+        res["K"][str(K)] = {
+            "ms": {k: {"median": round(med[k], 4), "min_max": [round(min(v), 4), round(max(v), 4)]} for k, v in ms.items()},
+            "region_on_over_off": {"median": round(statistics.median(ratios), 5),
+                                   "min_max": [round(min(ratios), 5), round(max(ratios), 5)]},
+            "score_ensemble_over_score": round(med["score_ensemble"] / med["score"], 5),
+            "member_launches_bytes_written": K * px * 4,
+            "main_bytes_floor": nbytes,
+            "main_memory_floor_ms": {k: round(v / (a.hbm_tbs * 1e12) * 1e3, 5) for k, v in nbytes.items()},
+            "main_time_over_floor": {k: round(med[k] / (v / (a.hbm_tbs * 1e12) * 1e3), 2) for k, v in nbytes.items()},
+            "main_tb_per_s": {k: round(v / (med[k] * 1e-3) / 1e12, 3) for k, v in nbytes.items()},
+            "workspace_kib": round(plain.workspace.numel() / 1024, 1),
+            "result": {k: round(float(got[k][0]), 6) for k in ("crps", "crps_fair", "rmse_mean", "spread_rms", "ssr",
+                                                                "spread_error_corr", "outliers", "outliers_expected",
+                                                                "reliability_index")},
+            "rank_hist": got["rank_hist"][0].tolist(), "tied": int(got["tied"][0]), "used": int(got["used"][0]),
+            "bin_spread": [round(float(v), 5) for v in got["bin_spread"][0]],
+            "bin_rmse": [round(float(v), 5) for v in got["bin_rmse"][0]],
+            "rmse_model": float(losses["model"])}
+        del runs, fn, on, off, plain, mapped, members, images, got
+        torch.cuda.empty_cache()
+    return res
+
+
 def consistency_main(a, spec, params, lr, dev, kw):
     from oracle.rcan_oracle import synthetic_hr
     from srmi.engine import downsample
@@ -985,6 +1075,8 @@ def main():
     ap.add_argument("--ssim", action="store_true", help="time score_ssim's SSIM stage beside score")
     ap.add_argument("--gradient", action="store_true", help="time score_gradient's stage beside score")
     ap.add_argument("--fss", action="store_true", help="time score_fss, its stage and each of its launches beside score")
+    ap.add_argument("--ensemble-score", action="store_true",
+                    help="time members=True, score_ensemble, the member launches and the score's launches at K = 4, 8")
     ap.add_argument("--hbm-tbs", type=float, default=6.3, help="achievable HBM rate the memory floor is taken at")
     ap.add_argument("--distribution", action="store_true",
                     help="time score_distribution's stage beside score and the SSIM stage, on a smooth and a white input")
@@ -996,15 +1088,15 @@ def main():
                     help="time the quantile map's launches and the region with the map on and off, and score both")
     ap.add_argument("--out", default=None, help="default: profiles/superres_bench.json (superres_land_bench.json, "
                                                 "spectra_bench.json, ssim_bench.json, gradient_bench.json, "
-                                                "fss_bench.json, "
+                                                "fss_bench.json, ensemble_score_bench.json, "
                                                 "distribution_bench.json, "
                                                 "ensemble_bench.json, consistency_bench.json, "
                                                 "quantile_map_bench.json)")
     a = ap.parse_args()
     if (sum(x is not None for x in (a.land, a.spectra, a.ensemble, a.consistent)) + a.ssim + a.distribution
-            + a.quantile_map + a.gradient + a.fss > 1):
-        raise SystemExit("superres_bench: --land, --spectra, --ssim, --gradient, --fss, --distribution, --ensemble, "
-                         "--consistent and --quantile-map are separate runs")
+            + a.quantile_map + a.gradient + a.fss + a.ensemble_score > 1):
+        raise SystemExit("superres_bench: --land, --spectra, --ssim, --gradient, --fss, --ensemble-score, --distribution, "
+                         "--ensemble, --consistent and --quantile-map are separate runs")
     if a.land is not None and not 0.0 < a.land < 1.0:
         raise SystemExit("superres_bench: --land takes a fraction in (0, 1)")
     if a.out is None:
@@ -1013,6 +1105,7 @@ def main():
                              "ssim_bench.json" if a.ssim else
                              "gradient_bench.json" if a.gradient else
                              "fss_bench.json" if a.fss else
+                             "ensemble_score_bench.json" if a.ensemble_score else
                              "distribution_bench.json" if a.distribution else
                              "ensemble_bench.json" if a.ensemble is not None else
                              "consistency_bench.json" if a.consistent is not None else
@@ -1033,12 +1126,13 @@ def main():
     lr = torch.tensor(synthetic_hr(1, 1, a.side, 99)[0]).to(dev)
     kw = {} if a.max_batch is None else {"max_batch": a.max_batch}
     if (a.land is not None or a.spectra is not None or a.ssim or a.distribution or a.ensemble is not None
-            or a.consistent is not None or a.quantile_map or a.gradient or a.fss):
+            or a.consistent is not None or a.quantile_map or a.gradient or a.fss or a.ensemble_score):
         line = json.dumps(land_main(a, spec, params, lr, dev, kw) if a.land is not None else
                           spectra_main(a, spec, params, dev, kw) if a.spectra is not None else
                           ssim_main(a, spec, params, dev, kw) if a.ssim else
                           gradient_main(a, spec, params, dev, kw) if a.gradient else
                           fss_main(a, spec, params, dev, kw) if a.fss else
+                          ensemble_score_main(a, spec, params, lr, dev, kw) if a.ensemble_score else
                           distribution_main(a, spec, params, dev, kw) if a.distribution else
                           ensemble_main(a, spec, params, lr, dev, kw) if a.ensemble is not None else
                           quantile_map_main(a, spec, params, dev, kw) if a.quantile_map else
